@@ -2,7 +2,7 @@
 """bench.py — throughput of the batched transform + log-abs-det-Jacobian hot path on MI355X.
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--workload c1|c2|c3|c4|c5a|c5b] [--scaling weak|strong]
-                    [--collective torch|bjx] [--no-rows]
+                    [--collective torch|bjx] [--full] [--no-rows] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
 A "step" = ONE pass of the hot path over one batch of synthetic input that is already resident in
@@ -10,12 +10,16 @@ HBM.  Default workload = BASELINE.json configs[1] ("c2"): with_logabsdet_jacobia
 exp ∘ Shift(b) ∘ Scale(a), Float32, dim = 64, batch = 2^24 PER GPU (weak scaling: every rank
 owns an independent column block; the only collective is the 8-byte all-reduce of Σ logabsdetjac).
 
-Prints ONE JSON line on rank 0 (contract in the task description) with `roofline` (algorithmic
-bytes / HIP-event time of the dominant kernel vs the 8 TB/s HBM peak) and `cpu_baseline`
-(the CPU oracle = a port of the reference algorithm, timed on the host cores of the same box on a
-bounded sample of the same workload).
+Prints ONE JSON line on rank 0 (contract in the task description).  A plain run does only what the headline needs: set-up,
+the W warm-up steps and the pre-roll, K timed steps (wall clock, nothing of ours on the stream) -> `value`, `ms_per_step`.
+`--dump-outputs DIR` then writes what the last timed step returned to its caller as DIR/<name>.npy (see `dump_outputs`).
 
-The same line carries `rows`: one measured sub-line per OTHER BASELINE.json config — c1 (configs[0], a Float64 vector
+`--full` adds everything else, each measured in passes of its own: `cold`, `roofline` (algorithmic bytes / HIP-event time of
+the dominant kernel vs the 8 TB/s HBM peak), `cpu_baseline` (the CPU oracle = a port of the reference algorithm, timed on
+the host cores of the same box on a bounded sample of the same workload), the sub-lines below and the side file
+bench_detail.json next to this file.
+
+With --full the same line carries `rows`: one measured sub-line per OTHER BASELINE.json config — c1 (configs[0], a Float64 vector
 of 2^20 through elementwise(exp): a launch-latency case, with its CPU leg), c3, c4, c5a, c5b — each with `kernel`,
 `kernel_ms`, `roofline.frac` and (N = 1) `cpu_baseline`, measured exactly like the headline (same barriers, hipEvent
 pairs on the context stream), so every BASELINE config is witnessed by whoever runs this file.  With N > 1 ranks the
@@ -51,6 +55,11 @@ def parse():
     p.add_argument("--collective", default="torch", choices=["torch", "bjx"],
                    help="who all-reduces the Float64 partial Σ logabsdetjac: torch.distributed (RCCL) or the library's own "
                         "communicator (bjx_comm_init + bjx_allreduce_sum_f64: the path a Julia host takes)")
+    p.add_argument("--full", action="store_true",
+                   help="also measure cold / roofline / cpu_baseline and the sub-lines (rows, strong_scaling, small_calls, graph_step), "
+                        "and write bench_detail.json; a plain run times the headline only")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="after the timed steps, write what the last one returned (y, log-dets) as DIR/<name>.npy")
     p.add_argument("--no-rows", action="store_true", help="only the headline workload (no per-config sub-lines)")
     p.add_argument("--rows", default="c1,c3,c3_uncached,c4,c5a,c5b,c2_f64,c4_f64")
     p.add_argument("--no-cache-params", action="store_true",
@@ -101,13 +110,20 @@ def compose_planar(bj, w, u, b):
 PREROLL_MS = float(os.environ.get("BJX_BENCH_PREROLL_MS", "60"))     # untimed clock-settling pre-roll before the timed steps (0 = off)
 
 # ---------------------------------------------------------------------------------- workloads
+RESULT = ("y", "logabsdetjac", "logabsdetjac_sum")      # what with_logabsdet_jacobian_sharded returns to its caller, in order
 DEFAULT_LOG2 = {"c1": 0, "c2": 24, "c2v": 24, "copy": 24, "c3": 22, "c4": 22, "c5a": 20, "c5b": 20, "vcorr": 18, "pdvec": 18, "c2_f64": 24, "c4_f64": 22}
 
 
 def make_workload(name, bj, torch, device, rank, world, log2_batch, scaling="weak"):
-    """-> dict(step=callable, samples=int on this rank, total=int over all ranks, bytes_per_sample, label, kernel, dtype, cfg)"""
+    """-> dict(step=callable, samples=int on this rank, total=int over all ranks, bytes_per_sample, label, kernel, dtype, cfg,
+    outputs=callable -> {name: tensor} of what the latest step returned to its caller)"""
     f32 = torch.float32
-    lb = DEFAULT_LOG2[name] if log2_batch is None else log2_batch
+    res = [None]                                   # the latest step's result tuple (one reference store per step)
+
+    def outputs():
+        return dict(zip(RESULT, res[0]))
+
+    lb =DEFAULT_LOG2[name] if log2_batch is None else log2_batch
     NG = 1 << lb                                   # the BASELINE batch
     if scaling == "strong":                        # fixed global batch, contiguous column blocks (SURVEY.md §8e)
         lo, hi = bj.shard.shard_columns(NG, world, rank)
@@ -127,9 +143,10 @@ def make_workload(name, bj, torch, device, rank, world, log2_batch, scaling="wea
         b = bj.elementwise(bj.exp)
 
         def step():
-            return sharded(b, x, out=y, per_sample=False)[2]
+            res[0] = r = sharded(b, x, out=y, per_sample=False)
+            return r[2]
 
-        return dict(step=step, samples=1, total=world, elements=n, bytes_per_sample=16 * n, kernel="chain_flat_kernel<double>", dtype="f64",
+        return dict(step=step, outputs=outputs, samples=1, total=world, elements=n, bytes_per_sample=16 * n, kernel="chain_flat_kernel<double>", dtype="f64",
                     label="with_logabsdet_jacobian(elementwise(exp)) Float64 vector of 2^20 (one call = one 'sample'; BASELINE configs[0])",
                     cfg={"workload": "elementwise(exp) + logabsdetjac on a Float64 Vector of 2^20 (BASELINE configs[0])", "length": n})
     if name in ("c2", "c2v", "copy"):
@@ -145,9 +162,10 @@ def make_workload(name, bj, torch, device, rank, world, log2_batch, scaling="wea
             b = bj.elementwise(bj.exp) @ bj.Shift(torch.full((dim,), 0.1, device=device)) @ bj.Scale(torch.linspace(0.5, 1.5, dim, device=device))
 
         def step():
-            return sharded(b, x, out=y, per_sample=False)[2]
+            res[0] = r = sharded(b, x, out=y, per_sample=False)
+            return r[2]
 
-        return dict(step=step, samples=N, total=total, bytes_per_sample=2 * dim * 4, kernel="chain_flat_kernel", dtype="f32",
+        return dict(step=step, outputs=outputs, samples=N, total=total, bytes_per_sample=2 * dim * 4, kernel="chain_flat_kernel", dtype="f32",
                     label=f"with_logabsdet_jacobian(exp∘Shift∘Scale) Float32 dim={dim} {where}",
                     cfg={"workload": "Composed(Shift,Scale,Exp) fused fwd+logabsdetjac (BASELINE configs[1])", "dim": dim,
                          "batch_per_gpu": N, "params": "scalar" if name == "c2" else "per-row vectors"})
@@ -164,11 +182,14 @@ def make_workload(name, bj, torch, device, rank, world, log2_batch, scaling="wea
         ib = bj.inverse(b)
 
         def step():
-            y_, _, s1 = sharded(b, x, out=y)
-            _, _, s2 = sharded(ib, y_, out=xb)
-            return s1
+            r = sharded(b, x, out=y)
+            res[0] = r + sharded(ib, r[0], out=xb)
+            return r[2]
 
-        return dict(step=step, samples=N, total=total, bytes_per_sample=(2 * dim * 4 + 4) * 2, kernel="rqs_lds_kernel (forward + inverse launch)", dtype="f32",
+        def outputs():                             # forward, then the inverse of its y
+            return dict(zip(RESULT + ("x", "logabsdetjac_inverse", "logabsdetjac_sum_inverse"), res[0]))
+
+        return dict(step=step, outputs=outputs, samples=N, total=total, bytes_per_sample=(2 * dim * 4 + 4) * 2, kernel="rqs_lds_kernel (forward + inverse launch)", dtype="f32",
                     label=f"RationalQuadraticSpline K=16 fwd+inverse+logabsdetjac Float32 dim={dim} {where}",
                     cfg={"workload": "RationalQuadraticSpline K=16 fwd+inv+logabsdetjac (BASELINE configs[2])", "dim": dim, "batch_per_gpu": N})
     if name in ("c2_f64", "c4_f64"):
@@ -184,9 +205,10 @@ def make_workload(name, bj, torch, device, rank, world, log2_batch, scaling="wea
             b = bj.elementwise(bj.exp) @ bj.Shift(0.1) @ bj.Scale(0.5)
 
             def step():
-                return sharded(b, x, out=y, per_sample=False)[2]
+                res[0] = r = sharded(b, x, out=y, per_sample=False)
+                return r[2]
 
-            return dict(step=step, samples=N64, total=total // 2, bytes_per_sample=2 * dim * 8, kernel="chain_flat_kernel<double>", dtype="f64",
+            return dict(step=step, outputs=outputs, samples=N64, total=total // 2, bytes_per_sample=2 * dim * 8, kernel="chain_flat_kernel<double>", dtype="f64",
                         label=f"with_logabsdet_jacobian(exp∘Shift∘Scale) Float64 dim={dim} batch=2^{lb - 1}/GPU",
                         cfg={"workload": "Composed(Shift,Scale,Exp) fused fwd+logabsdetjac, Float64 (configs[1] in the reference's test dtype)", "dim": dim, "batch_per_gpu": N64})
         dim, nl = 128, 8
@@ -201,9 +223,10 @@ def make_workload(name, bj, torch, device, rank, world, log2_batch, scaling="wea
         flow = compose_planar(bj, w, u, bb)
 
         def step():
-            return sharded(flow, x, out=y)[2]
+            res[0] = r = sharded(flow, x, out=y)
+            return r[2]
 
-        return dict(step=step, samples=N64, total=total // 2, bytes_per_sample=2 * dim * 8 + 8, kernel="planar_mfma64_kernel", dtype="f64",
+        return dict(step=step, outputs=outputs, samples=N64, total=total // 2, bytes_per_sample=2 * dim * 8 + 8, kernel="planar_mfma64_kernel", dtype="f64",
                     label=f"8-layer PlanarLayer flow fused fwd+logabsdetjac Float64 dim={dim} batch=2^{lb - 1}/GPU",
                     cfg={"workload": "l8∘…∘l1 of PlanarLayers (planner-fused), Float64 (configs[3] in the reference's test dtype)", "dim": dim, "layers": nl, "batch_per_gpu": N64})
     if name == "c4":
@@ -220,9 +243,10 @@ def make_workload(name, bj, torch, device, rank, world, log2_batch, scaling="wea
         flow = compose_planar(bj, w, u, bb)
 
         def step():
-            return sharded(flow, x, out=y)[2]
+            res[0] = r = sharded(flow, x, out=y)
+            return r[2]
 
-        return dict(step=step, samples=N, total=total, bytes_per_sample=2 * dim * 4 + 4, kernel="planar_reg2_kernel", dtype="f32",
+        return dict(step=step, outputs=outputs, samples=N, total=total, bytes_per_sample=2 * dim * 4 + 4, kernel="planar_reg2_kernel", dtype="f32",
                     label=f"8-layer PlanarLayer flow l8∘…∘l1 (planner: one fused launch) fwd+logabsdetjac Float32 dim={dim} {where}",
                     cfg={"workload": "l8∘…∘l1 of PlanarLayers, fused by the composition planner (BASELINE configs[3])", "dim": dim, "layers": nl, "batch_per_gpu": N})
     if name == "c5a":
@@ -233,9 +257,10 @@ def make_workload(name, bj, torch, device, rank, world, log2_batch, scaling="wea
         b = bj.SimplexBijector()
 
         def step():
-            return sharded(b, x)[2]
+            res[0] = r = sharded(b, x)
+            return r[2]
 
-        return dict(step=step, samples=N, total=total, bytes_per_sample=K * 4 + (K - 1) * 4 + 4, kernel="quad_stream_kernel<QSimplexFwd>", dtype="f32",
+        return dict(step=step, outputs=outputs, samples=N, total=total, bytes_per_sample=K * 4 + (K - 1) * 4 + 4, kernel="quad_stream_kernel<QSimplexFwd>", dtype="f32",
                     label=f"SimplexBijector fwd+logabsdetjac Float32 K={K} {where}",
                     cfg={"workload": "SimplexBijector (BASELINE configs[4], first half)", "K": K, "batch_per_gpu": N})
     if name == "c5b":
@@ -246,9 +271,10 @@ def make_workload(name, bj, torch, device, rank, world, log2_batch, scaling="wea
         ib = bj.inverse(bj.VecCholeskyBijector("U"))
 
         def step():
-            return sharded(ib, yv)[2]
+            res[0] = r = sharded(ib, yv)
+            return r[2]
 
-        return dict(step=step, samples=N, total=total, bytes_per_sample=n * 4 + K * K * 4 + 4, kernel="chol_inv_chunk_kernel", dtype="f32",
+        return dict(step=step, outputs=outputs, samples=N, total=total, bytes_per_sample=n * 4 + K * K * 4 + 4, kernel="chol_inv_chunk_kernel", dtype="f32",
                     label=f"inverse VecCholeskyBijector (y->W dense + logJ) Float32 K={K} {where}",
                     cfg={"workload": "VecCholeskyBijector inverse, dense W (BASELINE configs[4], second half)", "K": K, "batch_per_gpu": N})
     if name in ("vcorr", "pdvec"):
@@ -263,9 +289,10 @@ def make_workload(name, bj, torch, device, rank, world, log2_batch, scaling="wea
         del yv
 
         def step():
-            return sharded(b, X)[2]
+            res[0] = r = sharded(b, X)
+            return r[2]
 
-        return dict(step=step, samples=N, total=total, bytes_per_sample=K * K * 4 + n * 4 + 4, kernel="chol_link_kernel", dtype="f32",
+        return dict(step=step, outputs=outputs, samples=N, total=total, bytes_per_sample=K * K * 4 + n * 4 + 4, kernel="chol_link_kernel", dtype="f32",
                     label=f"{'VecCorrBijector' if name == 'vcorr' else 'PDVecBijector'} (X -> Cholesky -> y + logabsdetjac) Float32 K={K} {where}",
                     cfg={"workload": f"{'VecCorrBijector' if name == 'vcorr' else 'PDVecBijector'} forward (SURVEY.md §8f-4)", "K": K, "batch_per_gpu": N})
     raise ValueError(name)
@@ -410,7 +437,45 @@ def traffic_source(workload):
         return None
 
 
+# ---------------------------------------------------------------------------------- --dump-outputs
+DUMP_BYTES = 48 << 20      # all arrays of one dump together (64 MB allowed)
+DUMP_SEED = 0
+
+
+def dump_outputs(outputs, d):
+    """Writes every tensor of `outputs` ({name: float32 / float64 tensor}) as d/<name>.npy in its own dtype.  When the arrays
+    together exceed DUMP_BYTES, the ones whose last axis is the batch (the longest last axis) keep a sorted sample of its
+    columns drawn with DUMP_SEED: the same columns for every array, and the same from run to run for the same arguments."""
+    import numpy as np
+    import torch
+
+    arrays = {k: v.detach() for k, v in outputs.items() if v is not None}
+    n = max(t.shape[-1] if t.dim() else 1 for t in arrays.values())
+    batched = [k for k, t in arrays.items() if t.dim() and t.shape[-1] == n]
+    per_col = sum(arrays[k].numel() // n * arrays[k].element_size() for k in batched)
+    if per_col * n > DUMP_BYTES:
+        k_cols = max(1, DUMP_BYTES // per_col)
+        cols = torch.from_numpy(np.sort(np.random.default_rng(DUMP_SEED).choice(n, size=k_cols, replace=False)))
+        for k in batched:
+            t = arrays[k]
+            arrays[k] = t.index_select(t.dim() - 1, cols.to(t.device))
+    os.makedirs(d, exist_ok=True)
+    for k, t in arrays.items():
+        assert t.dtype in (torch.float32, torch.float64), (k, t.dtype)
+        np.save(os.path.join(d, k + ".npy"), t.cpu().numpy())
+
+
 # ---------------------------------------------------------------------------------- one measured workload
+KERNEL_TIME_MAX_LAUNCHES = 1024      # launches one bjx_kernel_time_begin/_end region records (include/bjx.h)
+
+
+def kernel_chunks(steps, launches_per_step):
+    """Step counts of the consecutive kernel-time regions that cover `steps` steps, none over KERNEL_TIME_MAX_LAUNCHES launches
+    when a step issues at most `launches_per_step` of them."""
+    per = max(1, KERNEL_TIME_MAX_LAUNCHES // max(1, math.ceil(launches_per_step)))
+    return [min(per, steps - i) for i in range(0, steps, per)]
+
+
 class Env:
     pass
 
@@ -443,9 +508,10 @@ def measure_small_calls(env, calls=400, reps=5):
     return out
 
 
-def measure(env, name, steps, warmup, scaling, log2_batch=None, want_cold=True):
+def measure(env, name, steps, warmup, scaling, log2_batch=None, want_cold=True, full=True, dump_dir=None):
     """Warm up, then time EXACTLY `steps` steps between barrier + synchronize on both sides; max over ranks.
-    -> dict on every rank (only rank 0 uses it)."""
+    full=False: the wall pass only (no `cold`, `roofline`, `passes`).  dump_dir: rank 0 writes the outputs of the wall pass's
+    last step there (`dump_outputs`).  -> dict on every rank (only rank 0 uses it)."""
     torch, bj, dist = env.torch, env.bj, env.dist
     wl = make_workload(name, bj, torch, env.device, env.rank, env.world, log2_batch, scaling)
     ctx = bj.context(env.device)
@@ -478,28 +544,43 @@ def measure(env, name, steps, warmup, scaling, log2_batch=None, want_cold=True):
           "kernel" — one hipEvent pair around every dominant-kernel launch: -> Σ ms, n  (`kernel_ms`, `roofline`)
         -> (wall s, stream-region ms, Σ dominant-kernel ms, launches)"""
         nonlocal last
+        # one kernel-time region records at most KERNEL_TIME_MAX_LAUNCHES launches: the kernel pass is cut into consecutive regions
+        # of whole steps, sized by the launches per step of the pass before it, and their sums are added
+        chunks = kernel_chunks(steps, launches_all[0] or 1) if instrument == "kernel" else [steps]
+        k_ms, k_n = 0.0, 0
+
+        def kernel_time_end():
+            nonlocal k_ms, k_n
+            ms, n = C.c_float(0.0), C.c_int(0)
+            bj._lib.check(ctx.h, lib.bjx_kernel_time_end(ctx.h, C.byref(ms), C.byref(n)), "bjx_kernel_time_end")
+            k_ms += ms.value
+            k_n += n.value
+
         if instrument == "kernel":
             lib.bjx_kernel_time_begin(ctx.h)      # prof_on = 1 (context stream)
         if instrument == "region":
             lib.bjx_time_begin(ctx.h)
         n_launch0 = lib.bjx_launch_count()
         t0 = time.perf_counter()
-        for _ in range(steps):
-            last = wl["step"]()
+        for i, n in enumerate(chunks):
+            if i:                                 # the region before is full: close it (synchronises the stream), open the next
+                kernel_time_end()
+                lib.bjx_kernel_time_begin(ctx.h)
+            for _ in range(n):
+                last = wl["step"]()
         launches_all[0] = (lib.bjx_launch_count() - n_launch0) / max(steps, 1)      # EVERY kernel launch of the library in the region (helpers included)
         ev_ms = C.c_float(0.0)
         if instrument == "region":
             lib.bjx_time_end(ctx.h, C.byref(ev_ms))
         barrier()
         dt = time.perf_counter() - t0
-        k_ms, k_n = C.c_float(0.0), C.c_int(0)
         if instrument == "kernel":
-            bj._lib.check(ctx.h, lib.bjx_kernel_time_end(ctx.h, C.byref(k_ms), C.byref(k_n)), "bjx_kernel_time_end")
+            kernel_time_end()
         if dist is not None:
-            tt = torch.tensor([dt, ev_ms.value, k_ms.value], dtype=torch.float64, device=env.device)
+            tt = torch.tensor([dt, ev_ms.value, k_ms], dtype=torch.float64, device=env.device)
             dist.all_reduce(tt, op=dist.ReduceOp.MAX)
-            return float(tt[0]), float(tt[1]), float(tt[2]), k_n.value
-        return dt, ev_ms.value, k_ms.value, k_n.value
+            return float(tt[0]), float(tt[1]), float(tt[2]), k_n
+        return dt, ev_ms.value, k_ms, k_n
 
     # COLD pass: the W warm-up steps as asked, then K timed steps — what a sampler's first calls or any burst shorter than ~30 ms
     # see (profiles/r03_warmup.md: a fresh process reaches its steady clocks only after 20-30 ms of load; C3 reads 0.54 of the
@@ -536,26 +617,29 @@ def measure(env, name, steps, warmup, scaling, log2_batch=None, want_cold=True):
             torch.cuda.synchronize()
         barrier()
     dt, _, _, _ = timed_pass("wall")
-    _, ev, _, _ = timed_pass("region")
-    dt_k, _, kern_total, k_launches = timed_pass("kernel")
-    ladj_total = float(last[0]) if last is not None else float("nan")
+    if dump_dir is not None and env.rank == 0:
+        dump_outputs(wl["outputs"](), dump_dir)
     ms_per_step = dt / steps * 1e3
-    # dominant kernel(s) of ONE step: per-launch hipEvent pairs summed, / steps (a step of c3 has two
-    # launches, forward + inverse, and `bytes_per_sample` counts both)
-    kern_ms = kern_total / steps
-    alg_bytes = wl["samples"] * wl["bytes_per_sample"]       # per step, one GPU
-    achieved = alg_bytes / (kern_ms * 1e-3) / 1e9 if kern_ms > 0 else float("nan")
     res = {
         "workload": name, "label": wl["label"], "value": wl["total"] / (dt / steps) / 1e6, "unit": "M samples/s", "dtype": wl["dtype"],
         "ms_per_step": ms_per_step, "steps": steps, "warmup": warmup, "preroll_steps": pre, "scaling": scaling, "config": wl["cfg"],
-        "roofline": {"bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": achieved / HBM_PEAK_GBS,
-                     "traffic": traffic_from_profiles(name), "traffic_source": traffic_source(name), "kernel": wl["kernel"], "kernel_ms": kern_ms,
-                     "kernel_launches_per_step": k_launches / max(steps, 1), "launches_per_step_all": launches_all[0], "stream_region_ms_per_step": ev / steps,
-                     "algorithmic_bytes_per_launch": alg_bytes, "frac_of_measured_copy_ceiling_6290": achieved / 6290.0},
-        "sum_logabsdetjac": ladj_total, "cold": cold,
-        "passes": {"wall_ms_per_step": ms_per_step, "kernel_pass_wall_ms_per_step": dt_k / steps * 1e3,
-                   "note": "value / ms_per_step / cold: pass without any event on the stream; kernel_ms: a separate pass with one hipEvent pair per launch"},
+        "cold": cold,
     }
+    if full:
+        _, ev, _, _ = timed_pass("region")
+        dt_k, _, kern_total, k_launches = timed_pass("kernel")
+        # dominant kernel(s) of ONE step: per-launch hipEvent pairs summed, / steps (a step of c3 has two
+        # launches, forward + inverse, and `bytes_per_sample` counts both)
+        kern_ms = kern_total / steps
+        alg_bytes = wl["samples"] * wl["bytes_per_sample"]       # per step, one GPU
+        achieved = alg_bytes / (kern_ms * 1e-3) / 1e9 if kern_ms > 0 else float("nan")
+        res["roofline"] = {"bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": achieved / HBM_PEAK_GBS,
+                           "traffic": traffic_from_profiles(name), "traffic_source": traffic_source(name), "kernel": wl["kernel"], "kernel_ms": kern_ms,
+                           "kernel_launches_per_step": k_launches / max(steps, 1), "launches_per_step_all": launches_all[0], "stream_region_ms_per_step": ev / steps,
+                           "algorithmic_bytes_per_launch": alg_bytes, "frac_of_measured_copy_ceiling_6290": achieved / 6290.0}
+        res["passes"] = {"wall_ms_per_step": ms_per_step, "kernel_pass_wall_ms_per_step": dt_k / steps * 1e3,
+                         "note": "value / ms_per_step / cold: pass without any event on the stream; kernel_ms: a separate pass with one hipEvent pair per launch"}
+    res["sum_logabsdetjac"] = float(last[0]) if last is not None else float("nan")
     if name == "c1":
         res["us_per_call"] = ms_per_step * 1e3
         res["M_elements_per_s"] = wl["elements"] * env.world / (dt / steps) / 1e6
@@ -637,15 +721,16 @@ def compact_row(r):
 def build_line(a, world, head, rows, graph_rows, strong, cpu):
     """The ONE JSON line of the contract.  Everything a reader needs to judge the number is in it; explanatory prose and the
     per-row detail (labels, CPU sample descriptions, traffic sources) live in the side file named by `detail`."""
-    rf = head["roofline"]
+    rf = head.get("roofline")         # measured with --full only
     out = {
         "metric": METRIC, "value": head["value"], "unit": "M samples/s", "n_gpus": world, "steps": a.steps, "warmup": a.warmup,
         "ms_per_step": head["ms_per_step"], "higher_is_better": True, "scaling": a.scaling, "vs_baseline": None,
         "dtype": head["dtype"], "data": "synthetic (Philox N(0,1), shard-invariant)",
         "config": dict(head["config"], parallelism=f"batch-sharded x{world}, one f64 all-reduce of Σlogabsdetjac ({a.collective})",
                        cache_params=not a.no_cache_params),
-        "roofline": {k: rf.get(k) for k in ("bound", "achieved", "peak", "unit", "frac", "traffic", "traffic_source", "kernel", "kernel_ms",
-                                            "kernel_launches_per_step", "launches_per_step_all", "stream_region_ms_per_step", "algorithmic_bytes_per_launch")},
+        "roofline": None if rf is None else {k: rf.get(k) for k in ("bound", "achieved", "peak", "unit", "frac", "traffic", "traffic_source", "kernel",
+                                                                    "kernel_ms", "kernel_launches_per_step", "launches_per_step_all",
+                                                                    "stream_region_ms_per_step", "algorithmic_bytes_per_launch")},
         "cpu_baseline": cpu,
         "preroll": {"ms": PREROLL_MS, "steps": head.get("preroll_steps", 0)},
         "passes": head.get("passes"),
@@ -745,9 +830,9 @@ def main():
         bj.shard.use_library_collective(True)               # watchdog: a stuck collective is an error after 60 s, not a hang
         env.library_collective = True
 
-    head = measure(env, a.workload, a.steps, a.warmup, a.scaling, a.log2_batch)
+    head = measure(env, a.workload, a.steps, a.warmup, a.scaling, a.log2_batch, want_cold=a.full, full=a.full, dump_dir=a.dump_outputs)
     rows, strong = [], []
-    want_rows = (not a.no_rows) and a.workload == "c2" and a.log2_batch is None
+    want_rows = a.full and (not a.no_rows) and a.workload == "c2" and a.log2_batch is None
     if want_rows:
         rsteps, rwarm = max(3, min(a.steps, 20)), max(1, min(a.warmup, 5))      # the sub-lines run as warm as the headline
         for r in [r for r in a.rows.split(",") if r]:
@@ -790,7 +875,7 @@ def main():
                 graph_rows.append({"workload": wl_, "log2_batch_per_gpu": lb, "error": repr(e)})
 
     if rank == 0:
-        cpu_ok = not a.no_cpu_baseline and world == 1
+        cpu_ok = a.full and not a.no_cpu_baseline and world == 1
         cpu = None
         if cpu_ok:
             try:
@@ -806,20 +891,18 @@ def main():
         out = build_line(a, world, head, rows if want_rows else [], graph_rows, strong, cpu)
         if small_rows:
             out["small_calls"] = small_rows
-        # the full record (labels, CPU sample descriptions, traffic sources, graph-step sums): a side file, best effort
-        detail = {"line": out, "head": head, "rows": rows, "graph_step": graph_rows, "strong_scaling": strong,
-                  "notes": {"preroll": "untimed steps of the same workload after the W warm-up steps, until the GPU has been under load for `ms` (steady clocks); the timed region is exactly K steps",
-                            "cold": "K timed steps right after the W warm-up steps, no pre-roll: what a burst shorter than ~30 ms sees",
-                            "traffic": "roofline.traffic is the rocprofv3 PMC measurement stored in profiles/traffic.json (not measured in this run)"}}
-        for d in (os.path.join(ROOT, "gpurun_out"), ROOT):
+        if a.full:
+            # the full record (labels, CPU sample descriptions, traffic sources, graph-step sums): a side file next to this one, best effort
+            detail = {"line": out, "head": head, "rows": rows, "graph_step": graph_rows, "strong_scaling": strong,
+                      "notes": {"preroll": "untimed steps of the same workload after the W warm-up steps, until the GPU has been under load for `ms` (steady clocks); the timed region is exactly K steps",
+                                "cold": "K timed steps right after the W warm-up steps, no pre-roll: what a burst shorter than ~30 ms sees",
+                                "traffic": "roofline.traffic is the rocprofv3 PMC measurement stored in profiles/traffic.json (not measured in this run)"}}
             try:
-                os.makedirs(d, exist_ok=True)
-                with open(os.path.join(d, "bench_detail.json"), "w") as f:
+                with open(os.path.join(ROOT, "bench_detail.json"), "w") as f:
                     json.dump(detail, f, indent=1)
-                out["detail"] = os.path.relpath(os.path.join(d, "bench_detail.json"), ROOT)
-                break
+                out["detail"] = "bench_detail.json"
             except Exception:
-                continue
+                pass
         print(json.dumps(out, separators=(",", ":")))
     if dist is not None:
         dist.barrier()

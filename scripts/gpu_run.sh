@@ -10,7 +10,7 @@
 #   gpu_run.sh rowprof <filter> ["<counters>" ...]  rocprofv3 kernel stats (+ --pmc passes, kernel-trace only) of scripts/bench_rows.py --only <filter>
 #   gpu_run.sh stats <workload>               rocprofv3 --kernel-trace --stats of one bench workload      -> gpurun_out/<wl>_kernel_stats.csv
 #   gpu_run.sh profile <TAG> [workloads...]   the round's evidence, everything under gpurun_out/<TAG>/ (scripts/collect_profiles.py <TAG>
-#                                             turns it into profiles/): pytest -m gpu, the default bench line, one bench line + kernel
+#                                             turns it into profiles/): pytest -m gpu, the default bench line (--full), one bench line + kernel
 #                                             stats + FETCH_SIZE / WRITE_SIZE passes per workload, the rows tables, .so size and first-call latency
 cd "$GRAFT_REPO_ROOT" 2>/dev/null || cd /root/repo
 export TMPDIR=/tmp
@@ -80,11 +80,11 @@ profile)
   python scripts/probe_first_call.py > $O/first_call.txt 2>&1
   cat $O/first_call.txt
   rm -f gpurun_out/matrix_vjp_errors.jsonl gpurun_out/vjp_errors.jsonl $O/kernel_trace_timed.jsonl
-  echo "== default bench line (what the driver runs: first on a fresh box)"; timeout 900 python bench.py > $O/bench_default.json 2>$O/bench_default.err; wc -c $O/bench_default.json; cp gpurun_out/bench_detail.json $O/bench_default_detail.json 2>/dev/null
+  echo "== default bench line, --full (first on a fresh box)"; timeout 900 python bench.py --full > $O/bench_default.json 2>$O/bench_default.err; wc -c $O/bench_default.json; cp bench_detail.json $O/bench_default_detail.json 2>/dev/null
   echo "== pytest -m gpu"; ( time timeout 1500 python -m pytest tests -m gpu -q --maxfail=25 -p no:cacheprovider ) > $O/pytest_gpu.txt 2>&1; tail -4 $O/pytest_gpu.txt
   cp gpurun_out/matrix_vjp_errors.jsonl gpurun_out/vjp_errors.jsonl $O/ 2>/dev/null
   for wl in $WLS; do
-    timeout 600 python bench.py --workload $wl --no-rows --steps 20 --warmup 5 2>$O/bench_$wl.err | tail -1 > $O/bench_$wl.json; echo "== bench $wl: $(cut -c1-120 $O/bench_$wl.json)"
+    timeout 600 python bench.py --workload $wl --full --no-rows --steps 20 --warmup 5 2>$O/bench_$wl.err | tail -1 > $O/bench_$wl.json; echo "== bench $wl: $(cut -c1-120 $O/bench_$wl.json)"
   done
   echo "== rows tables (table and kernel stats from the SAME process)"
   ( cd /tmp && timeout 900 rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof_rows -o rows -- python $R/scripts/bench_rows.py > $O/rows_raw.txt 2>&1 )
@@ -108,7 +108,7 @@ profile)
     done
   done
   for wl in $WLS; do
-    ( cd /tmp && timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof_$wl -o $wl -- python $R/bench.py --workload $wl --steps 20 --warmup 5 --no-cpu-baseline --no-rows > $O/rocprof_$wl.log 2>&1 )
+    ( cd /tmp && timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof_$wl -o $wl -- python $R/bench.py --workload $wl --full --steps 20 --warmup 5 --no-cpu-baseline --no-rows > $O/rocprof_$wl.log 2>&1 )
     f=$(ls $O/prof_$wl/*kernel_stats.csv 2>/dev/null | head -1); [ -n "$f" ] && { cp "$f" $O/${wl}_kernel_stats.csv; echo "-- kernel stats $wl"; head -3 "$f" | cut -c1-160; }
     # the same trace, timed launches only (after bench.py's pre-roll): median / min / mean — what the line's kernel_ms must agree with
     f=$(ls $O/prof_$wl/*kernel_trace.csv 2>/dev/null | head -1); [ -n "$f" ] && python scripts/trace_stats.py "$f" $wl 60 >> $O/kernel_trace_timed.jsonl

@@ -1,5 +1,5 @@
-"""profiles/<TAG>_bench_repeats.md from the profile set's line and gpurun_out/bench_rep_*.json (one `python bench.py > gpurun_out/bench_rep_N.json`
-per gpurun call = one fresh box each):   python scripts/make_bench_repeats.py r06"""
+"""profiles/<TAG>_bench_repeats.md from the profile set's line and the repeat lines bench_rep_*.json in the GPU runs' output directory
+(one `python bench.py --full > bench_rep_N.json` per fresh box):   python scripts/make_bench_repeats.py r06"""
 import glob
 import json
 import os
@@ -31,7 +31,7 @@ def main():
         if d:
             boxes.append((f"fresh box {os.path.basename(p)[10:-5]}", d))
     n = len(boxes)
-    out = [f"# {tag} — the driver's line (`python bench.py`, no flags) on {n} fresh boxes with the shipped library (`profiles/{tag}_lib_sha16.txt`)", "",
+    out = [f"# {tag} — the driver's line (`python bench.py --full`) on {n} fresh boxes with the shipped library (`profiles/{tag}_lib_sha16.txt`)", "",
            "One gpurun call per row = one fresh box; nothing ran on the box before the line.  M samples/s unless noted; bars of BASELINE.md: C2 ≥ 9 370, C3 ≥ 9 300, C4 ≥ 4 670, C5a ≥ 9 370, C5b ≥ 196.",
            "", "| box | C2 headline | frac | C3 (table kept) | C3 frac | C3 (default: table rebuilt) | C4 | C5a | C5b | C2 f64 | C4 f64 | C1 µs/call | small calls µs |", "|---|" + "---|" * 12]
     cs = []

@@ -4,7 +4,7 @@
 
   trace_stats.py <kernel_trace.csv> <workload> [last_n]
 
-bench.py runs, per workload: warm-up, a cold pass, the pre-roll (≥ 60 ms of the same step), then THREE timed passes of `steps` steps.
+bench.py --full runs, per workload: warm-up, a cold pass, the pre-roll (≥ 60 ms of the same step), then THREE timed passes of `steps` steps.
 The last `last_n` launches of every distinct dominant kernel (default 60 = 3 passes × 20 steps) are those timed passes."""
 import csv
 import json

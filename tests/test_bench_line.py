@@ -82,3 +82,62 @@ def test_gpus_n_without_a_launcher_starts_n_ranks(tmp_path, monkeypatch):
     assert len({e["MASTER_PORT"] for _, e, _ in seen}) == 1 and [e["LOCAL_RANK"] for _, e, _ in seen] == ["0", "1", "2", "3"]
     assert all(argv[2:] == ["--gpus", "4", "--steps", "3"] for argv, _, _ in seen)
     assert "".join(out) == '{"n_gpus": 4}\n'
+
+
+def test_a_plain_line_carries_the_headline_only(monkeypatch):
+    """A plain run (no --full) times the headline alone: the line keeps the contract's fields and says null for what it did not measure."""
+    import bench
+
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "7", "--warmup", "2"])
+    a = bench.parse()
+    assert not a.full and a.dump_outputs is None and a.steps == 7
+    head = {k: v for k, v in _fake_row("c2", bench).items() if k not in ("roofline", "cold", "cpu_baseline")}
+    line = bench.build_line(a, 1, head, [], [], [], None)
+    for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"):
+        assert line[k] is not None, k
+    assert line["ms_per_step"] == head["ms_per_step"] and line["steps"] == 7
+    assert line["roofline"] is None and line["cpu_baseline"] is None and line["cold"] is None and "rows" not in line
+
+
+def test_dump_outputs_writes_a_seeded_sample_of_the_same_columns(tmp_path):
+    """--dump-outputs: float32 / float64 arrays, at most 64 MB together; a batch too large for that keeps the same seeded columns in
+    every array, from run to run."""
+    import numpy as np
+    import torch
+
+    import bench
+
+    n = 1 << 20
+    col = torch.arange(n, dtype=torch.float32)
+    outs = {"y": col.double()[None, :] * 100 + torch.arange(16, dtype=torch.float64)[:, None], "logabsdetjac": col.clone(),
+            "logabsdetjac_sum": torch.tensor([3.5], dtype=torch.float64), "absent": None}
+    for d in ("a", "b"):
+        bench.dump_outputs(outs, str(tmp_path / d))
+    files = sorted(p.name for p in (tmp_path / "a").iterdir())
+    assert files == ["logabsdetjac.npy", "logabsdetjac_sum.npy", "y.npy"]
+    assert sum((tmp_path / "a" / f).stat().st_size for f in files) <= 64 << 20
+    y, l, s = (np.load(tmp_path / "a" / f) for f in ("y.npy", "logabsdetjac.npy", "logabsdetjac_sum.npy"))
+    assert y.dtype == np.float64 and l.dtype == np.float32 and s.dtype == np.float64 and s.tolist() == [3.5]
+    assert y.shape[0] == 16 and 1 < y.shape[1] < n and l.shape == (y.shape[1],)
+    assert np.array_equal(y[0] / 100, l) and np.all(np.diff(l) > 0)                  # the same sorted columns in both arrays
+    np.testing.assert_array_equal(y[5], l.astype(np.float64) * 100 + 5)
+    for f in files:
+        assert np.array_equal(np.load(tmp_path / "a" / f), np.load(tmp_path / "b" / f))
+    small = {"y": torch.ones(4, 8, dtype=torch.float64)}                              # under the budget: written whole
+    bench.dump_outputs(small, str(tmp_path / "c"))
+    assert np.load(tmp_path / "c" / "y.npy").shape == (4, 8)
+
+
+def test_the_kernel_pass_never_overfills_a_kernel_time_region():
+    """The library records at most 1024 launches per bjx_kernel_time_begin/_end region: `--full --steps K` with K x launches per step
+    above that cuts the kernel pass into regions of whole steps that together are exactly K steps."""
+    import bench
+
+    for steps, per_step in ((20, 3.0), (1093, 1.0), (3000, 3.0), (5000, 2.5), (7, 2000.0), (1, 1.0), (0, 3.0)):
+        chunks = bench.kernel_chunks(steps, per_step)
+        assert sum(chunks) == steps and all(c > 0 for c in chunks), (steps, per_step, chunks)
+        if per_step <= bench.KERNEL_TIME_MAX_LAUNCHES:
+            assert all(c * per_step <= bench.KERNEL_TIME_MAX_LAUNCHES for c in chunks), (steps, per_step, chunks)
+    assert bench.kernel_chunks(20, 3.0) == [20] and len(bench.kernel_chunks(3000, 3.0)) == 9
+    header = open(os.path.join(ROOT, "include", "bjx.h")).read()
+    assert f"(at most {bench.KERNEL_TIME_MAX_LAUNCHES} per region)" in header
