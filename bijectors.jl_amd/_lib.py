@@ -144,6 +144,13 @@ SIGNATURES = {
     "bjx_graph_destroy": (_i, [_vp]),
 }
 
+# include/bjx_cols.h (the companion header: bjx.h and SIGNATURES stay as they are)
+BJX_COLS_KNOTS, BJX_COLS_RAW = 0, 1
+SIGNATURES_COLS = {
+    "bjx_rqs_cols": (_i, [_vp, _i, _i, _i, _vp, _i64, _vp, _vp, _vp, _i64, _i64, _i64, _i, _d, _vp, _vp] + _tail),
+    "bjx_rqs_cols_vjp": (_i, [_vp, _i, _i, _i, _vp, _i64, _vp, _vp, _vp, _i64, _i64, _i64, _i, _d, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64]),
+}
+
 _lib = None
 
 
@@ -158,10 +165,10 @@ def load() -> C.CDLL:
             "(hipcc --offload-arch=gfx950).  There is no CPU fallback."
         )
     lib = C.CDLL(LIB_PATH, mode=C.RTLD_GLOBAL)
-    missing = [n for n in SIGNATURES if not hasattr(lib, n)]
+    missing = [n for n in list(SIGNATURES) + list(SIGNATURES_COLS) if not hasattr(lib, n)]
     if missing:  # an incomplete ABI is a build error, not something to paper over
         raise ImportError(f"{LIB_PATH} does not export {missing}; rebuild it")
-    for name, (res, args) in SIGNATURES.items():
+    for name, (res, args) in list(SIGNATURES.items()) + list(SIGNATURES_COLS.items()):
         fn = getattr(lib, name)
         fn.restype = res
         fn.argtypes = args

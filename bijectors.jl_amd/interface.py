@@ -1811,11 +1811,34 @@ class RationalQuadraticSpline(Bijector):
 
     RationalQuadraticSpline(widths, heights, derivatives)          — knot arrays as in :79-97
     RationalQuadraticSpline(widths, heights, derivatives, B)       — raw (dim,K),(dim,K),(dim,K-1) via :109-123
+
+    With 3-D tensors the spline has one parameter set per COLUMN of the batch (what a Coupling's θ returns for a batch of
+    samples — the neural spline coupling): knots (dim, K+1, batch), or the raw form (dim, K, batch), (dim, K, batch),
+    (dim, K-1, batch) with B, which stays raw (the B constructor runs inside the spline kernel, include/bjx_cols.h).  Tensors
+    laid out column-major per column — a `permute(2, 1, 0)` view of a (batch, m, dim) network output, or a slice of one — are
+    passed with their column stride and no copy.  The reference's `derivatives > 0` check (:94) is not evaluated for 3-D knots
+    (it would be a host pass over batch-sized data); the raw form guarantees it.  For the raw 3-D form the attributes
+    `widths` / `heights` / `derivatives` hold the unconstrained parameters.
     """
 
     def __init__(self, widths, heights, derivatives, B=None):
         self._raw = None
+        self._cols = None         # per-column spline: (form, K, B)
         w, h, d = (torch.as_tensor(t) for t in (widths, heights, derivatives))
+        if w.dim() == 3:
+            if h.dim() != 3 or d.dim() != 3:
+                raise ValueError("DimensionMismatch: per-column spline parameters must all be 3-D (dim, m, batch)")
+            dim, m, nb = w.shape
+            if B is None:
+                if tuple(h.shape) != tuple(w.shape) or tuple(d.shape) != tuple(w.shape) or m < 2:
+                    raise ValueError("DimensionMismatch: expected widths/heights/derivatives (dim, K+1, batch)")
+                self._cols = (L.BJX_COLS_KNOTS, m - 1, 0.0)
+            else:
+                if tuple(h.shape) != tuple(w.shape) or tuple(d.shape) != (dim, m - 1, nb):
+                    raise ValueError("DimensionMismatch: expected raw widths/heights (dim, K, batch) and derivatives (dim, K-1, batch)")
+                self._cols = (L.BJX_COLS_RAW, m, float(B))
+            self.widths, self.heights, self.derivatives = w, h, d
+            return
         if w.dim() == 1:
             w, h, d = w[None, :], h[None, :], d[None, :]
         if B is not None:
@@ -1842,10 +1865,33 @@ class RationalQuadraticSpline(Bijector):
     def _key(self):
         return tuple(_keyify(t) for t in (self.widths, self.heights, self.derivatives))
 
+    def _col_params(self, like, batch):
+        """-> (p_w, p_h, p_d, ld_w, ld_h, ld_d) for bjx_rqs_cols: each tensor column-major per column ([r + j*n + col*ld]); a
+        tensor already laid out so (a permuted network output or a slice of one) is passed as it is, anything else is made so once."""
+        if int(self.widths.shape[2]) != batch:
+            raise ValueError(f"DimensionMismatch: spline parameters for {int(self.widths.shape[2])} columns applied to {batch} columns")
+        outs, lds = [], []
+        for t in (self.widths, self.heights, self.derivatives):
+            if t.device != like.device or t.dtype != like.dtype:
+                t = t.to(device=like.device, dtype=like.dtype)
+            t = t.detach()
+            n, m, nb = t.shape
+            ok = (t.stride(0) == 1 or n <= 1) and (t.stride(1) == n or m <= 1) and (t.stride(2) >= n * m or nb <= 1)
+            if not ok:
+                t = t.permute(2, 1, 0).contiguous().permute(2, 1, 0)
+            outs.append(t)
+            lds.append(int(t.stride(2)) if nb > 1 else n * m)
+        return outs + lds
+
     def _run(self, x, inv, per_sample, want_ladj):
         xc, dim, batch, vec = _prep(x)
         if dim != self.widths.shape[0]:
             raise ValueError(f"DimensionMismatch: spline with {self.widths.shape[0]} rows applied to {dim} rows")
+        if self._cols is not None:
+            form, K, B = self._cols
+            pw, ph, pd, lw, lh, ld = self._col_params(xc, batch)
+            return _call_struct("bjx_rqs_cols", x, dim, False, per_sample, want_ladj,
+                                (int(inv), form, None, dim, _ptr(pw), _ptr(ph), _ptr(pd), lw, lh, ld, K, B), (dim,))
         w, h, d = (colmajor(_param(t, xc)) for t in (self.widths, self.heights, self.derivatives))
         _note_params(context(xc.device), w, h, d)           # under `cache_params` an unchanged spline keeps its LDS blob (BJX_OPT_PARAM_EPOCH)
         return _call_struct("bjx_rqs", x, dim, False, per_sample, want_ladj,
@@ -1903,7 +1949,8 @@ class Coupling(Bijector):
     """coupling.jl:174-259.  θ maps x₂ (rows of partition 2, shape (n2[, batch])) to a bijector for x₁.
     θ runs on the host side (it is an arbitrary closure, SURVEY.md §8b last row); the laws it may
     return that have device kernels are `Shift`, `Scale`, `Shift @ Scale` with parameters of shape
-    (n1[, batch]) and `RationalQuadraticSpline` with (n1, K+1) knots."""
+    (n1[, batch]) and `RationalQuadraticSpline` with (n1, K+1) knots shared by the batch, or with per-sample (n1, m, batch)
+    parameters (knots or the raw B-constructor form: one parameter set per column, bjx_rqs_cols — the neural spline coupling)."""
 
     def __init__(self, theta, mask):
         if isinstance(mask, int):  # coupling.jl:183-186
@@ -1919,6 +1966,14 @@ class Coupling(Bijector):
         law = self.theta(self.mask.rows2(xc))
         idx1 = self.mask.idx1_dev(xc.device)
         n1 = idx1.numel()
+        if isinstance(law, RationalQuadraticSpline) and law._cols is not None:
+            # per-sample knots (the neural spline coupling): one parameter set per column, bjx_rqs_cols on the rows of x₁
+            if int(law.widths.shape[0]) != n1:
+                raise ValueError(f"DimensionMismatch: spline with {int(law.widths.shape[0])} rows for a partition of {n1} rows")
+            form, K, B = law._cols
+            pw, ph, pd, lw, lh, ld = law._col_params(xc, batch)
+            return _call_struct("bjx_rqs_cols", x, dim, False, per_sample, want_ladj,
+                                (int(inv), form, _ptr(idx1), n1, _ptr(pw), _ptr(ph), _ptr(pd), lw, lh, ld, K, B), (dim,))
         if isinstance(law, RationalQuadraticSpline):
             w, h, d = (colmajor(_param(t, xc)) for t in (law.widths, law.heights, law.derivatives))
             return _call_struct("bjx_coupling_rqs", x, dim, False, per_sample, want_ladj,
@@ -1958,10 +2013,22 @@ class Coupling(Bijector):
     def _wlj_inv(self, x, per_sample, want_ladj=True):
         return self._run(x, True, per_sample, want_ladj)
 
-    def _vjp(self, x, out_bar, ladj_bar, inv):
+    def _theta_grad(self, outs, cots, x2, params):
+        """θ's pullback by torch.autograd: the cotangent of x₂ and, with `params`, of θ's named parameters (nn.Module)."""
+        named = list(self.theta.named_parameters()) if params and isinstance(self.theta, torch.nn.Module) else []
+        named = [(k, p_) for k, p_ in named if p_.requires_grad]
+        if not outs:
+            return None, ({k: torch.zeros_like(p_) for k, p_ in named} if params and isinstance(self.theta, torch.nn.Module) else None)
+        gs = torch.autograd.grad(outs, [x2] + [p_ for _, p_ in named], cots, allow_unused=True)
+        th = {k: (g_ if g_ is not None else torch.zeros_like(p_)) for (k, p_), g_ in zip(named, gs[1:])}
+        return gs[0], (th if params and isinstance(self.theta, torch.nn.Module) else None)
+
+    def _vjp(self, x, out_bar, ladj_bar, inv, params=False):
         """Pullback of the affine coupling (bjx_coupling_affine_vjp): x̄ with the x₁ rows scaled and the rest passed
         through, plus — when θ is made of torch operations — the part that flows back through θ's outputs
-        (s̄, t̄ from the kernel, θ's own pullback by torch.autograd on the host: θ is an arbitrary closure)."""
+        (s̄, t̄ from the kernel, θ's own pullback by torch.autograd on the host: θ is an arbitrary closure).
+        params=True: (x̄, grads) with the law's cotangents shaped like θ's outputs (see `vjp_params`) and, when θ is a
+        torch.nn.Module, grads["theta"] = {name: gradient} of its named parameters."""
         xc, dim, batch, vec = _prep(x)
         gc, gdim, gbatch, _ = _prep(out_bar)
         if dim != self.mask.n or (gdim, gbatch) != (dim, batch) or gc.dtype != xc.dtype:
@@ -1970,6 +2037,26 @@ class Coupling(Bijector):
         x2 = xc[i2].detach().clone().requires_grad_(True) if vec else xc[i2, :].detach().clone().requires_grad_(True)
         with torch.enable_grad():
             law = self.theta(x2)
+            if isinstance(law, RationalQuadraticSpline) and law._cols is not None:
+                # per-sample spline law (bjx_rqs_cols_vjp): x̄ on the x₁ rows and the per-column parameter cotangents in one pass,
+                # ȳ passed through on the other rows; the cotangents go back through θ onto x₂ (and θ's weights)
+                idx1 = self.mask.idx1_dev(xc.device)
+                if int(law.widths.shape[0]) != idx1.numel():
+                    raise ValueError(f"DimensionMismatch: spline with {int(law.widths.shape[0])} rows for a partition of {idx1.numel()} rows")
+                ts = (law.widths, law.heights, law.derivatives)
+                want = tuple(bool(params or t.requires_grad) for t in ts)
+                xb, kb = _rqs_cols_pullback(law, inv, xc, gc, ladj_bar, dim, batch, vec, idx1=idx1, want=want)
+                names = ("widths", "heights", "derivatives") if law._cols[0] == L.BJX_COLS_KNOTS else ("raw_widths", "raw_heights", "raw_derivatives")
+                outs = [t for t in ts if t.requires_grad]
+                cots = [kb[k].to(t.dtype) for k, t in zip(names, ts) if t.requires_grad]
+                g2, th = self._theta_grad(outs, cots, x2, params)
+                if g2 is not None:
+                    xb[i2] += g2
+                if not params:
+                    return xb
+                if th is not None:
+                    kb["theta"] = th
+                return xb, kb
             if isinstance(law, RationalQuadraticSpline):
                 # spline law (coupling.jl:206-259 with b = RationalQuadraticSpline(w, h, d), knots shared by the batch):
                 # x̄₁ = the elementwise spline pullback on the x₁ rows (bjx_rqs_vjp), every other row passes ȳ through.
@@ -1982,6 +2069,20 @@ class Coupling(Bijector):
                 knots = [t for t in (law.widths, law.heights, law.derivatives)]
                 through_theta = any(isinstance(t, torch.Tensor) and t.requires_grad for t in knots)
                 xb = gc.clone() if vec else colmajor(gc.clone())
+                if params:
+                    plain = RationalQuadraticSpline(*[t.detach() for t in knots])
+                    sub, kb = _vjp_params_rqs(inverse(plain) if inv else plain, x1, g1, ladj_bar)
+                    xb[i1] = sub
+                    outs = [t for t in knots if isinstance(t, torch.Tensor) and t.requires_grad]
+                    cots = [kb[n].reshape(t.shape).to(t.dtype) for n, t in zip(("widths", "heights", "derivatives"), knots)
+                            if isinstance(t, torch.Tensor) and t.requires_grad]
+                    g2, th = self._theta_grad(outs, cots, x2, True)
+                    if g2 is not None:
+                        xb[i2] += g2
+                    grads = {k: kb[k] for k in ("widths", "heights", "derivatives")}
+                    if th is not None:
+                        grads["theta"] = th
+                    return xb, grads
                 if not through_theta:
                     xb[i1] = vjp(inverse(law) if inv else law, x1, g1, ladj_bar)
                     return xb
@@ -2031,6 +2132,21 @@ class Coupling(Bijector):
             if f_ is not None and f_.requires_grad:
                 outs.append(f_)
                 cots.append(b_.reshape(-1) if vec else b_)
+        if params:
+            g2, th = self._theta_grad(outs, cots, x2, True)
+            if g2 is not None:
+                if vec:
+                    xb[i2] += g2
+                else:
+                    xb[i2, :] += g2
+            grads = {}
+            if sb is not None:
+                grads["scale"] = sb.reshape(-1) if vec else sb
+            if tb is not None:
+                grads["shift"] = tb.reshape(-1) if vec else tb
+            if th is not None:
+                grads["theta"] = th
+            return xb, grads
         if outs:                                   # θ depends on x₂ through torch ops: add its pullback to the x₂ rows
             g2, = torch.autograd.grad(outs, [x2], cots, allow_unused=True)
             if g2 is not None:
@@ -2565,6 +2681,8 @@ def vjp(b, x, out_bar, ladj_bar=None):
             raise ValueError("DimensionMismatch: out_bar must have the shape and dtype of the output")
         if dim != base.widths.shape[0]:
             raise ValueError(f"DimensionMismatch: spline with {base.widths.shape[0]} rows applied to {dim} rows")
+        if base._cols is not None:
+            return _rqs_cols_pullback(base, inv, xc, gc, ladj_bar, dim, batch, vec, want=(False, False, False))[0]
         w, h, d = (colmajor(_param(t, xc)) for t in (base.widths, base.heights, base.derivatives))
         lb = _ladj_bar(ladj_bar, batch, xc)
         ctx = context(xc.device)
@@ -2872,10 +2990,17 @@ def vjp_params(b, x, out_bar, ladj_bar=None):
     shapes of b.w / b.u / b.b (bjx_planar_vjp_params; closed-form derivatives of planar_layer.jl:65-110).
     For a RadialLayer: (x_bar, {"alpha_", "beta", "z_0"}) — see _vjp_params_radial.
     For inverse(PlanarLayer) / inverse(RadialLayer): the same dictionaries through the implicit function theorem — see _vjp_params_inverse.
-    For a RationalQuadraticSpline or its inverse: (x_bar, {"widths", "heights", "derivatives"[, "raw_widths", ...]}) — see _vjp_params_rqs.
+    For a RationalQuadraticSpline or its inverse: (x_bar, {"widths", "heights", "derivatives"[, "raw_widths", ...]}) — see _vjp_params_rqs
+    (a per-column spline, 3-D parameters: the per-column cotangents in its own form, see _rqs_cols_pullback).
+    For a Coupling or its inverse: (x_bar, grads) with the cotangents of θ's outputs — {"scale", "shift"} per column (affine law),
+    {"widths", "heights", "derivatives"} summed over the batch (shared knots), the per-column spline's dictionary — and, when θ is
+    a torch.nn.Module, grads["theta"] = {name: gradient} for its named_parameters() (training a flow).
     For a chain that starts with Scale and/or Shift: (z_bar, {"scale": σ̄, "shift": μ̄}) — see _vjp_params_leading_affine.
     For a chain with Scale / Shift stages anywhere else: (x_bar, {"stages": [...]}) — see _vjp_params_affine_anywhere.
     For a composition that contains flow layers / splines / BatchNorm: (x_bar, {"stages": [...]}) — see _vjp_params_composed."""
+    if isinstance(b, Coupling) or (isinstance(b, Inverse) and isinstance(b.orig, Coupling)):
+        inv = isinstance(b, Inverse)
+        return (b.orig if inv else b)._vjp(x, out_bar, ladj_bar, inv, params=True)
     if isinstance(b, Inverse) and isinstance(b.orig, (PlanarLayer, RadialLayer)):
         return _vjp_params_inverse(b, x, out_bar, ladj_bar)
     if isinstance(b, RadialLayer):
@@ -2947,6 +3072,8 @@ def _vjp_params_rqs(b, x, out_bar, ladj_bar=None):
         raise ValueError("DimensionMismatch: out_bar must have the shape and dtype of the output")
     if dim != sp.widths.shape[0]:
         raise ValueError(f"DimensionMismatch: spline with {sp.widths.shape[0]} rows applied to {dim} rows")
+    if sp._cols is not None:
+        return _rqs_cols_pullback(sp, inv, xc, gc, ladj_bar, dim, batch, vec)
     w, h, d = (colmajor(_param(t, xc)) for t in (sp.widths, sp.heights, sp.derivatives))
     K1 = int(sp.widths.shape[1])
     lb = _ladj_bar(ladj_bar, batch, xc)
@@ -2965,6 +3092,26 @@ def _vjp_params_rqs(b, x, out_bar, ladj_bar=None):
         L.check(ctx.h, rc, "bjx_rqs_params_vjp")
         grads.update({"raw_widths": routs[0], "raw_heights": routs[1], "raw_derivatives": routs[2][:, :K - 1]})
     return xb, grads
+
+
+def _rqs_cols_pullback(sp, inv, xc, gc, ladj_bar, dim, batch, vec, idx1=None, want=(True, True, True)):
+    """bjx_rqs_cols_vjp for a per-column spline `sp` (3-D parameters) on the rows idx1 (None: every row): -> (x_bar, grads) with
+    the PER-COLUMN cotangents of the spline's tensors in its own form — {"widths", "heights", "derivatives"} (dim, K+1, batch)
+    or {"raw_widths", "raw_heights", "raw_derivatives"} (dim, K, batch), (dim, K, batch), (dim, K-1, batch) — for the entries of
+    `want` that are set.  One pass over x, ȳ, ℓ̄ and the parameters; nothing is summed over the batch."""
+    form, K, B = sp._cols
+    pw, ph, pd, lw, lh, ld = sp._col_params(xc, batch)
+    n = dim if idx1 is None else int(idx1.numel())
+    ms = (K + 1, K + 1, K + 1) if form == L.BJX_COLS_KNOTS else (K, K, K - 1)
+    bars = [torch.empty((batch, m, n), dtype=xc.dtype, device=xc.device).permute(2, 1, 0) if w_ else None for m, w_ in zip(ms, want)]
+    lb = _ladj_bar(ladj_bar, batch, xc)
+    ctx = context(xc.device)
+    xb = _empty(dim, batch, xc, vec)
+    rc = L.load().bjx_rqs_cols_vjp(ctx.h, _dt(xc), int(inv), form, _ptr(idx1), n, _ptr(pw), _ptr(ph), _ptr(pd), lw, lh, ld, K, B,
+                                   _ptr(xc), _ptr(gc), _ptr(lb), _ptr(xb), *[_ptr(b_) for b_ in bars], dim, batch)
+    L.check(ctx.h, rc, "bjx_rqs_cols_vjp")
+    keys = ("widths", "heights", "derivatives") if form == L.BJX_COLS_KNOTS else ("raw_widths", "raw_heights", "raw_derivatives")
+    return xb, {k: b_ for k, b_ in zip(keys, bars) if b_ is not None}
 
 
 def _vjp_params_batchnorm(bn, x, out_bar, ladj_bar=None):

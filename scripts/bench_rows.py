@@ -48,6 +48,7 @@ def main():
     xpos = torch.exp(0.5 * x.T).T
     xunit = torch.sigmoid(x.T).T
     rows = []  # (name, reference, callable, bytes_per_sample, samples)
+    torch_cols = []  # plain-PyTorch batched spline (softmax / cumsum / searchsorted / gather): the same coupling without bjx_rqs_cols
 
     def add(name, ref, b, inp, out_rows=None, per_sample=True, samples=None):
         n = inp.shape[-1] if samples is None else samples
@@ -241,6 +242,44 @@ def main():
     xmix[32:48] = xunit[32:48]
     add("Stacked(exp∘Shift∘Scale | Simplex | Logit | Ordered) d=64 → 63: structured blocks in the same launch", "f-4", mix, xmix, out_rows=d - 1)
 
+    # Per-column spline coupling (include/bjx_cols.h, the neural spline coupling): dim 64, half mask (n1 = 32), K = 8 bins,
+    # 2^20 columns Float32 / 2^19 Float64.  Algorithmic bytes: every parameter value once, x read and y written for every row, the
+    # per-sample log-det; the pullback reads the parameters, x₁, ȳ and ℓ̄ and writes x̄ and the per-column parameter cotangents.
+    if not only_given(a.only) or "RQS-cols" in a.only or "torch-spline" in a.only:
+        for dtc, lgN in ((torch.float32, 20), (torch.float64, 19)):
+            Nc_, n1c, Kc, Bc = 1 << lgN, 32, 8, 3.0
+            es = 4 if dtc == torch.float32 else 8
+            gq = torch.Generator(device=dev).manual_seed(9)
+            xq = torch.randn((Nc_, d), dtype=dtc, device=dev, generator=gq).T * 1.5
+            gy = torch.randn((Nc_, d), dtype=dtc, device=dev, generator=gq).T
+            lq = torch.randn(Nc_, dtype=dtc, device=dev, generator=gq)
+            head = torch.randn((Nc_, 3 * Kc - 1, n1c), dtype=dtc, device=dev, generator=gq).permute(2, 1, 0)    # one network head
+            rwq, rhq, rdq = head[:, :Kc], head[:, Kc:2 * Kc], head[:, 2 * Kc:]
+            sp_raw = bj.RationalQuadraticSpline(rwq, rhq, rdq, Bc)
+
+            def knots_t(r):
+                c_ = torch.cumsum(torch.softmax(r, dim=1), dim=1)
+                return torch.cat([torch.zeros_like(c_[:, :1]), c_], dim=1) * (2 * Bc) - Bc
+            one = torch.ones_like(rdq[:, :1])
+            kw, kh = knots_t(rwq), knots_t(rhq)
+            kd = torch.cat([one, torch.nn.functional.softplus(rdq), one], dim=1)
+            kw, kh, kd = (t.permute(2, 1, 0).contiguous().permute(2, 1, 0) for t in (kw, kh, kd))
+            sp_kn = bj.RationalQuadraticSpline(kw, kh, kd)
+            maskc = bj.PartitionMask(d, list(range(1, n1c + 1)))
+            cpl = {f: bj.Coupling((lambda s_: (lambda x2: s_))(s_), maskc) for f, s_ in (("raw", sp_raw), ("knots", sp_kn))}
+            P = {"raw": (3 * Kc - 1) * n1c * es, "knots": 3 * (Kc + 1) * n1c * es}
+            tag = "f32" if dtc == torch.float32 else "f64"
+            for form in ("raw", "knots"):
+                cb_ = cpl[form]
+                yq = torch.empty_like(xq)
+                bps_f = P[form] + 2 * d * es + es
+                bps_v = 2 * P[form] + (n1c + 2 * d) * es + es
+                rows.append((f"RQS-cols coupling {form} {tag} d=64 n1=32 K=8", "cols", (lambda c_=cb_, y_=yq, x_=xq: bj.shard.with_logabsdet_jacobian_sharded(c_, x_, out=y_)), bps_f, Nc_))
+                rows.append((f"RQS-cols inverse(coupling) {form} {tag} d=64 n1=32 K=8", "cols", (lambda c_=cb_, y_=yq, x_=xq: bj.shard.with_logabsdet_jacobian_sharded(bj.inverse(c_), x_, out=y_)), bps_f, Nc_))
+                rows.append((f"RQS-cols vjp_params(coupling) {form} {tag} (x̄ + per-column cotangents)", "cols", (lambda c_=cb_, x_=xq, g_=gy, l_=lq: bj.vjp_params(c_, x_, g_, l_)), bps_v, Nc_))
+                rows.append((f"RQS-cols vjp_params(inverse(coupling)) {form} {tag} (x̄ + per-column cotangents)", "cols", (lambda c_=cb_, x_=xq, g_=gy, l_=lq: bj.vjp_params(bj.inverse(c_), x_, g_, l_)), bps_v, Nc_))
+            torch_cols.append((tag, xq, rwq, rhq, rdq, Bc, n1c, P["raw"] + 2 * d * es + es, Nc_))
+
     only = [s for s in a.only.split(",") if s]
     L, ctx = bj._lib, bj.context(dev)
     lib = L.load()
@@ -262,6 +301,59 @@ def main():
             print(f"| {name} | {ref} | {k:.4f} | 2^{int(math.log2(n))} | {bps} | {gbs:.0f} | {100 * gbs / PEAK:.1f} | {reg:.4f} | {100 * gbr / PEAK:.1f} |", flush=True)
         except Exception as ex:  # keep the table going
             print(f"| {name} | {ref} | failed: {ex!r} | | | | | | |", flush=True)
+    for tag, xq, rwq, rhq, rdq, Bc, n1c, bps, n in torch_cols:
+        if only and not any(o in "torch-spline" for o in only) and not any("RQS-cols" in o for o in only):
+            continue
+        ms = torch_spline_ms(xq, rwq, rhq, rdq, Bc, n1c, a.steps)
+        gbs = bps * n / (ms * 1e-3) / 1e9
+        print(f"| torch-spline: plain PyTorch batched spline coupling, raw form {tag} (softmax / cumsum / searchsorted / gather) | cols | | 2^{int(math.log2(n))} | {bps} | {gbs:.0f} | {100 * gbs / PEAK:.1f} | {ms:.4f} | {100 * gbs / PEAK:.1f} |", flush=True)
+
+
+def only_given(s):
+    return bool([t for t in s.split(",") if t])
+
+
+def torch_spline_forward(x, rw, rh, rd, B, n1):
+    """The forward coupling with per-column raw spline parameters in plain PyTorch (what a user writes without bjx_rqs_cols)."""
+    x1 = x[:n1].T                                             # (N, n1)
+    def knots(r):
+        c = torch.cumsum(torch.softmax(r.permute(2, 0, 1).contiguous(), dim=-1), dim=-1)        # (N, n1, K)
+        return torch.cat([torch.zeros_like(c[..., :1]), c], dim=-1) * (2 * B) - B
+    w, h = knots(rw), knots(rh)
+    one = torch.ones_like(w[..., :1])
+    dd = torch.cat([one, torch.nn.functional.softplus(rd.permute(2, 0, 1).contiguous()), one], dim=-1)
+    inside = (x1 > -B) & (x1 < B)
+    k = torch.searchsorted(w.contiguous(), x1.unsqueeze(-1).contiguous()).clamp(1, w.shape[-1] - 1)
+    g = lambda t, i: torch.gather(t, -1, i).squeeze(-1)
+    wl, wu, hl, hu, dl, du = g(w, k - 1), g(w, k), g(h, k - 1), g(h, k), g(dd, k - 1), g(dd, k)
+    wd, dy = wu - wl, hu - hl
+    s = dy / wd
+    xi = (x1 - wl) / wd
+    om = 1 - xi
+    den = s + (du + dl - 2 * s) * xi * om
+    y1 = hl + dy * (s * xi * xi + dl * xi * om) / den
+    lj = torch.log(s * s * (du * xi * xi + 2 * s * xi * om + dl * om * om)) - 2 * torch.log(den)
+    y = x.clone()
+    y[:n1] = torch.where(inside, y1, x1).T
+    return y, torch.where(inside, lj, torch.zeros_like(lj)).sum(-1)
+
+
+def torch_spline_ms(x, rw, rh, rd, B, n1, steps, chunk=1 << 16):
+    """Stream time of the plain-PyTorch coupling, in slices of `chunk` columns (torch.cumsum rejects one launch over 2^25 rows)."""
+    def run():
+        for c0 in range(0, x.shape[1], chunk):
+            sl = slice(c0, c0 + chunk)
+            torch_spline_forward(x[:, sl], rw[:, :, sl], rh[:, :, sl], rd[:, :, sl], B, n1)
+    for _ in range(3):
+        run()
+    torch.cuda.synchronize()
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    e0.record()
+    for _ in range(steps):
+        run()
+    e1.record()
+    torch.cuda.synchronize()
+    return e0.elapsed_time(e1) / steps
 
 
 if __name__ == "__main__":
