@@ -83,7 +83,7 @@ def ref_spline(orc, W, H, D, x, inverse):
     return ys, ls
 
 
-SHAPES = [(1, 1, 5), (7, 5, 333), (16, 8, 1000), (32, 16, 257), (3, 32, 65), (64, 10, 64), (5, 4, 40)]
+SHAPES = [(1, 1, 5), (7, 5, 333), (16, 8, 1000), (32, 16, 257), (3, 32, 65), (64, 10, 64), (5, 4, 40), (6, 2, 100), (4, 64, 50)]
 
 
 @pytest.mark.parametrize("dt", [np.float32, np.float64])
@@ -276,21 +276,23 @@ def _loss(bj, b, x, g, lb):
 
 @pytest.mark.parametrize("inverse", [False, True])
 @pytest.mark.parametrize("with_lb", [True, False])
-def test_coupling_pullback_matches_oracle_and_autograd_through_theta(bj, orc, inverse, with_lb):
+@pytest.mark.parametrize("dt,mname", [(np.float64, "scattered"), (np.float64, "range"), (np.float32, "scattered"), (np.float32, "range")])
+def test_coupling_pullback_matches_oracle_and_autograd_through_theta(bj, orc, dt, mname, inverse, with_lb):
+    """The reference evaluates θ in Float64 on the host from the same weights and x (in Float32: the device runs θ in Float32)."""
     rng = np.random.default_rng(33)
     dim, K, N, B = 8, 8, 512, 3.0
-    mask = bj.PartitionMask(dim, masks(dim)["scattered"])
+    mask = bj.PartitionMask(dim, masks(dim)[mname])
     n1 = len(mask.indices_1)
     torch.manual_seed(2)
-    th = Head(dim - n1, n1, K, B, torch.float64).cuda()
+    th = Head(dim - n1, n1, K, B, DT[dt]).cuda()
     cl = bj.Coupling(th, mask)
-    x = rng.normal(size=(dim, N)) * 2
-    g = rng.normal(size=(dim, N))
-    lb = rng.normal(size=N) if with_lb else None
-    xb = bj.vjp(bj.inverse(cl) if inverse else cl, dev2(x, np.float64), dev2(g, np.float64), None if lb is None else torch.from_numpy(lb).cuda())
+    x = (rng.normal(size=(dim, N)) * 2).astype(dt).astype(np.float64)
+    g = rng.normal(size=(dim, N)).astype(dt).astype(np.float64)
+    lb = rng.normal(size=N).astype(dt).astype(np.float64) if with_lb else None
+    xb = bj.vjp(bj.inverse(cl) if inverse else cl, dev2(x, dt), dev2(g, dt), None if lb is None else torch.from_numpy(lb.astype(dt)).cuda())
     # reference: the oracle's per-column cotangents, then θ's pullback by torch.autograd on the CPU
     i1, i2 = np.array(mask.indices_1) - 1, np.array(mask.indices_2) - 1
-    thc = copy.deepcopy(th).cpu()
+    thc = copy.deepcopy(th).cpu().double()
     x2 = torch.from_numpy(np.ascontiguousarray(x[i2])).requires_grad_(True)
     hd = thc.head(x2)
     raw = [host(hd[:, :K]), host(hd[:, K:2 * K]), host(hd[:, 2 * K:])]
@@ -301,7 +303,7 @@ def test_coupling_pullback_matches_oracle_and_autograd_through_theta(bj, orc, in
     ref = g.copy()
     ref[i1] = xb1
     ref[i2] += g2.numpy()
-    flat_close(host(xb), ref, np.float64, f"coupling rqs_cols x̄ inv={inverse}")
+    flat_close(host(xb), ref, dt, f"coupling rqs_cols x̄ {mname} inv={inverse}")
 
 
 def test_coupling_pullback_matches_finite_differences(bj):
