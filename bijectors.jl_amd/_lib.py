@@ -151,6 +151,15 @@ SIGNATURES_COLS = {
     "bjx_rqs_cols_vjp": (_i, [_vp, _i, _i, _i, _vp, _i64, _vp, _vp, _vp, _i64, _i64, _i64, _i, _d, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64]),
 }
 
+# include/bjx_coupling.h (Coupling with a per-sample elementwise-chain law): params / ld_params / params_bar are arrays of 2·n_ops
+# entries, slot 2k + j = parameter j of stage k
+BJX_COUPLING_MAX_OPS = 4
+OP_AFFINE = 32
+SIGNATURES_COUPLING = {
+    "bjx_coupling_chain": (_i, [_vp, _i, _i, _vp, _i64, C.POINTER(BjxOp), _i, C.POINTER(_vp), C.POINTER(_i64), _vp, _vp] + _tail),
+    "bjx_coupling_chain_vjp": (_i, [_vp, _i, _i, _vp, _i64, C.POINTER(BjxOp), _i, C.POINTER(_vp), C.POINTER(_i64), _vp, _vp, _vp, _vp, C.POINTER(_vp), _i64, _i64]),
+}
+
 _lib = None
 
 
@@ -165,10 +174,10 @@ def load() -> C.CDLL:
             "(hipcc --offload-arch=gfx950).  There is no CPU fallback."
         )
     lib = C.CDLL(LIB_PATH, mode=C.RTLD_GLOBAL)
-    missing = [n for n in list(SIGNATURES) + list(SIGNATURES_COLS) if not hasattr(lib, n)]
+    missing = [n for n in list(SIGNATURES) + list(SIGNATURES_COLS) + list(SIGNATURES_COUPLING) if not hasattr(lib, n)]
     if missing:  # an incomplete ABI is a build error, not something to paper over
         raise ImportError(f"{LIB_PATH} does not export {missing}; rebuild it")
-    for name, (res, args) in list(SIGNATURES.items()) + list(SIGNATURES_COLS.items()):
+    for name, (res, args) in list(SIGNATURES.items()) + list(SIGNATURES_COLS.items()) + list(SIGNATURES_COUPLING.items()):
         fn = getattr(lib, name)
         fn.restype = res
         fn.argtypes = args

@@ -1945,6 +1945,107 @@ class PartitionMask:
         return t
 
 
+def _affine_law(law):
+    """(scale, shift) when the coupling law is Shift, Scale or Shift ∘ Scale (the laws of bjx_coupling_affine), else None."""
+    scale = shift = None
+    for s in (law._stages() if isinstance(law, ComposedFunction) else [law]):
+        if isinstance(s, Scale) and scale is None and shift is None:
+            scale = s.a
+        elif isinstance(s, Shift) and shift is None:
+            shift = s.a
+        else:
+            return None
+    return scale, shift
+
+
+_LAW_SUPPORTED = ("Shift, Scale, Shift∘Scale, RQS, or a chain of at most 4 elementwise stages — exp, log, Shift, Scale, inverse(Scale), "
+                  "Logit, inverse(Logit), LeakyReLU, SignFlip, a Scale directly followed by a Shift counting as one — with scalar, (n1,) "
+                  "or (n1, batch) parameters")
+
+
+def _law_stage(s):
+    """(op kind, [(attribute, value), ...]) of one elementwise stage of a coupling law, or None."""
+    if s is identity:
+        return L.OP_IDENTITY, []
+    if isinstance(s, Elementwise):
+        return s._ops()[0][0], []
+    inv = isinstance(s, Inverse)
+    o = s.orig if inv else s
+    if isinstance(o, Scale):                       # a 2-D `a` is per-sample here, as in the affine law
+        return (L.OP_SCALE_INV if inv else L.OP_SCALE), [("a", o.a)]
+    if isinstance(o, Logit):
+        return (L.OP_LOGIT_INV if inv else L.OP_LOGIT), [("a", o.a), ("b", o.b)]
+    if isinstance(o, SignFlip):
+        return L.OP_SIGNFLIP, []
+    if inv:
+        return None
+    if isinstance(o, Shift):
+        return L.OP_SHIFT, [("a", o.a)]
+    if isinstance(o, LeakyReLU):
+        return L.OP_LEAKY_RELU, [("alpha", o.alpha)]
+    return None
+
+
+class _ChainLaw:
+    """A coupling law marshalled for bjx_coupling_chain (include/bjx_coupling.h): the op list, and per parameter slot its source —
+    a host scalar, a (n1,) vector broadcast over the columns, or a (n1, batch) array with its own leading dimension."""
+
+    def __init__(self, law, xc, n1, batch, vec):
+        stages = law._stages() if isinstance(law, ComposedFunction) else [law]
+        parsed = []
+        for si, st in enumerate(stages):
+            ks = _law_stage(st)
+            if ks is None:
+                raise NotImplementedError(f"coupling law {law!r} has no device kernel: {type(st).__name__} is not an elementwise stage (supported: {_LAW_SUPPORTED})")
+            parsed.append((ks[0], [(si, attr, val) for attr, val in ks[1]]))
+        fused = []                                  # Scale directly followed by Shift: one BJX_OP_AFFINE stage
+        for kind, ps in parsed:
+            if kind == L.OP_SHIFT and fused and fused[-1][0] == L.OP_SCALE:
+                fused[-1] = (L.OP_AFFINE, fused[-1][1] + ps)
+            else:
+                fused.append((kind, ps))
+        if not fused or len(fused) > L.BJX_COUPLING_MAX_OPS:
+            raise NotImplementedError(f"coupling law {law!r} has no device kernel: {len(fused)} stages (supported: {_LAW_SUPPORTED})")
+        self.n = len(fused)
+        self.n_stages = len(stages)
+        self.ops = (L.BjxOp * self.n)()
+        self.params = (C.c_void_p * (2 * self.n))()
+        self.lds = (C.c_int64 * (2 * self.n))()
+        self.keep, self.slots = [], []              # slots: (slot, stage index, attribute, θ's tensor or None, source)
+        for k, (kind, ps) in enumerate(fused):
+            o = self.ops[k]
+            o.kind, o.param_len, o.p0, o.p1, o.v0, o.v1 = kind, 0, 0.0, 0.0, None, None
+            for j, (si, attr, val) in enumerate(ps):
+                src, t, ld = self._source(val, xc, n1, batch, vec)
+                if src == "scalar":
+                    setattr(o, f"p{j}", t)
+                else:
+                    self.keep.append(t)
+                    self.params[2 * k + j] = t.data_ptr()
+                    self.lds[2 * k + j] = ld
+                self.slots.append((2 * k + j, si, attr, val if isinstance(val, torch.Tensor) else None, src))
+
+    @staticmethod
+    def _source(p, xc, n1, batch, vec):
+        if isinstance(p, (list, tuple)):
+            p = torch.as_tensor(p, dtype=xc.dtype, device=xc.device)
+        if not isinstance(p, torch.Tensor) or p.dim() == 0:
+            return "scalar", float(p), 0
+        t = p.detach()
+        if t.device != xc.device or t.dtype != xc.dtype:
+            t = t.to(device=xc.device, dtype=xc.dtype)
+        if t.dim() == 1:
+            if t.numel() != n1:
+                raise ValueError(f"DimensionMismatch: coupling parameter of length {t.numel()} for {n1} rows")
+            return ("col", t.contiguous(), max(n1, 1)) if vec else ("row", t.contiguous(), 0)
+        if t.dim() != 2 or tuple(t.shape) != (n1, batch):
+            raise ValueError(f"DimensionMismatch: coupling parameter of shape {tuple(t.shape)} for ({n1}, {batch})")
+        # a column-major array, or a row slice of one (a head of a wider network output), is passed as it is
+        if not ((t.stride(0) == 1 or n1 <= 1) and (t.stride(1) >= n1 or batch <= 1)):
+            t = t.T.contiguous().T
+        return "col", t, (int(t.stride(1)) if batch > 1 else max(n1, 1))
+
+
 class Coupling(Bijector):
     """coupling.jl:174-259.  θ maps x₂ (rows of partition 2, shape (n2[, batch])) to a bijector for x₁.
     θ runs on the host side (it is an arbitrary closure, SURVEY.md §8b last row); the laws it may
@@ -1978,15 +2079,13 @@ class Coupling(Bijector):
             w, h, d = (colmajor(_param(t, xc)) for t in (law.widths, law.heights, law.derivatives))
             return _call_struct("bjx_coupling_rqs", x, dim, False, per_sample, want_ladj,
                                 (int(inv), _ptr(idx1), n1, _ptr(w), _ptr(h), _ptr(d), int(law.widths.shape[1])), (dim,))
-        scale = shift = None
-        stages = law._stages() if isinstance(law, ComposedFunction) else [law]
-        for s in stages:
-            if isinstance(s, Scale) and scale is None and shift is None:
-                scale = s.a
-            elif isinstance(s, Shift) and shift is None:
-                shift = s.a
-            else:
-                raise NotImplementedError(f"coupling law {law!r} has no device kernel (supported: Shift, Scale, Shift∘Scale, RQS)")
+        affine = _affine_law(law)
+        if affine is None:
+            # any other elementwise chain with per-sample parameters: bjx_coupling_chain (raises NotImplementedError for the rest)
+            m = _ChainLaw(law, xc, n1, batch, vec)
+            return _call_struct("bjx_coupling_chain", x, dim, False, per_sample, want_ladj,
+                                (int(inv), _ptr(idx1), n1, m.ops, m.n, m.params, m.lds), (dim,))
+        scale, shift = affine
 
         def full(p, bcast_flag):
             """-> (device array, flag): a scalar or (n1,) parameter stays T[n1] (broadcast over the columns inside the kernel)."""
@@ -2022,6 +2121,51 @@ class Coupling(Bijector):
         gs = torch.autograd.grad(outs, [x2] + [p_ for _, p_ in named], cots, allow_unused=True)
         th = {k: (g_ if g_ is not None else torch.zeros_like(p_)) for (k, p_), g_ in zip(named, gs[1:])}
         return gs[0], (th if params and isinstance(self.theta, torch.nn.Module) else None)
+
+    def _vjp_chain(self, law, inv, xc, gc, ladj_bar, dim, batch, vec, x2, i2, params):
+        """Pullback for an elementwise-chain law (bjx_coupling_chain_vjp): x̄ on the x₁ rows and the per-column cotangent of every
+        per-sample parameter in one pass, ȳ passed through on the other rows; the cotangents go back through θ onto x₂ (and θ's
+        weights).  params=True: grads["params"] = one dict per stage of the law (application order), {attribute: (n1, batch) cotangent}
+        for its per-sample parameters.  A scalar or (n1,) parameter that requires grad has a cotangent summed over the batch, which
+        this entry does not produce: NotImplementedError."""
+        idx1 = self.mask.idx1_dev(xc.device)
+        n1 = idx1.numel()
+        m = _ChainLaw(law, xc, n1, batch, vec)
+        bars = (C.c_void_p * (2 * m.n))()
+        cots = {}
+        for slot, si, attr, orig, src in m.slots:
+            if src != "col":
+                if orig is not None and orig.requires_grad:
+                    raise NotImplementedError(f"the cotangent of the {src} parameter `{attr}` of stage {si} is a sum over the batch; "
+                                              "only (n1, batch) parameters of a coupling law have a device pullback")
+                continue
+            if params or (orig is not None and orig.requires_grad):
+                cots[slot] = torch.empty((batch, n1), dtype=xc.dtype, device=xc.device).T
+                bars[slot] = cots[slot].data_ptr()
+        lb = _ladj_bar(ladj_bar, batch, xc)
+        ctx = context(xc.device)
+        xb = _empty(dim, batch, xc, vec)
+        rc = L.load().bjx_coupling_chain_vjp(ctx.h, _dt(xc), int(inv), _ptr(idx1), n1, m.ops, m.n, m.params, m.lds, _ptr(xc), _ptr(gc), _ptr(lb),
+                                             _ptr(xb), bars, dim, batch)
+        L.check(ctx.h, rc, "bjx_coupling_chain_vjp")
+        outs, ocots = [], []
+        for slot, si, attr, orig, src in m.slots:
+            if slot in cots and orig is not None and orig.requires_grad:
+                outs.append(orig)
+                ocots.append(cots[slot].reshape(orig.shape).to(orig.dtype))
+        g2, th = self._theta_grad(outs, ocots, x2, params)
+        if g2 is not None:
+            xb[i2] += g2
+        if not params:
+            return xb
+        per_stage = [{} for _ in range(m.n_stages)]
+        for slot, si, attr, orig, src in m.slots:
+            if slot in cots:
+                per_stage[si][attr] = cots[slot].reshape(-1) if vec else cots[slot]
+        grads = {"params": per_stage}
+        if th is not None:
+            grads["theta"] = th
+        return xb, grads
 
     def _vjp(self, x, out_bar, ladj_bar, inv, params=False):
         """Pullback of the affine coupling (bjx_coupling_affine_vjp): x̄ with the x₁ rows scaled and the rest passed
@@ -2095,14 +2239,10 @@ class Coupling(Bijector):
                 if g2 is not None:
                     xb[i2] += g2
                 return xb
-            scale = shift = None
-            for st in (law._stages() if isinstance(law, ComposedFunction) else [law]):
-                if isinstance(st, Scale) and scale is None and shift is None:
-                    scale = st.a
-                elif isinstance(st, Shift) and shift is None:
-                    shift = st.a
-                else:
-                    raise NotImplementedError(f"no device pullback for the coupling law {law!r} (affine laws only)")
+            affine = _affine_law(law)
+            if affine is None:
+                return self._vjp_chain(law, inv, xc, gc, ladj_bar, dim, batch, vec, x2, i2, params)
+            scale, shift = affine
             n1 = len(self.mask.indices_1)
 
             def full(p):

@@ -280,6 +280,62 @@ def main():
                 rows.append((f"RQS-cols vjp_params(inverse(coupling)) {form} {tag} (x̄ + per-column cotangents)", "cols", (lambda c_=cb_, x_=xq, g_=gy, l_=lq: bj.vjp_params(bj.inverse(c_), x_, g_, l_)), bps_v, Nc_))
             torch_cols.append((tag, xq, rwq, rhq, rdq, Bc, n1c, P["raw"] + 2 * d * es + es, Nc_))
 
+    # Coupling with a per-sample elementwise-chain law (include/bjx_coupling.h): dim 64, half mask (n1 = 32), Float32.  The yardstick
+    # is the affine law Shift ∘ Scale with per-sample parameters on the existing kernels (bjx_coupling_affine / _vjp); the same law as
+    # ONE affine stage of bjx_coupling_chain / _vjp is called through the C entry (the Python Coupling keeps the affine entries for it).
+    # Algorithmic bytes: x read and y written for every row, the per-sample log-det, every per-sample parameter value once; the
+    # pullback reads x, ȳ, ℓ̄ and the parameters and writes x̄ and one cotangent per parameter value.
+    if not only_given(a.only) or "Coupling-chain" in a.only:
+        n1c = 32
+        I = bj.interface
+        gq = torch.Generator(device=dev).manual_seed(11)
+        head = torch.randn((N, 4 * n1c), dtype=f32, device=dev, generator=gq).T                       # one network head: s1, t1, s2, t2
+        sc1, sh1 = 0.5 + torch.sigmoid(head[:n1c].T).T, 0.5 * head[n1c:2 * n1c]
+        sc2, sh2 = 0.5 + torch.sigmoid(head[2 * n1c:3 * n1c].T).T, 0.5 * head[3 * n1c:]
+        del head
+        gyc = randn(d, N, dev, 5)
+        lqc = torch.randn(N, dtype=f32, device=dev, generator=gq)
+        maskc = bj.PartitionMask(d, list(range(1, n1c + 1)))
+        aff = lambda: bj.Shift(sh1) @ bj.Scale(sc1, batched=True)
+        laws = {
+            "affine Shift∘Scale": (aff(), x, 2),
+            "gated inverse(Logit(0,1))∘Shift∘Scale∘Logit(0,1)": (bj.inverse(bj.Logit(0.0, 1.0)) @ aff() @ bj.Logit(0.0, 1.0), xunit, 2),
+            "exp∘Shift∘Scale": (e(bj.exp) @ aff(), x, 2),
+            "inverse(Logit(-1,2))∘Shift∘Scale": (bj.inverse(bj.Logit(-1.0, 2.0)) @ aff(), x, 2),
+            "LeakyReLU(0.2)∘Shift∘Scale": (bj.LeakyReLU(0.2) @ aff(), x, 2),
+            "Shift∘Scale∘LeakyReLU(0.3)∘Shift∘Scale": (bj.Shift(sh2) @ bj.Scale(sc2, batched=True) @ bj.LeakyReLU(0.3) @ aff(), x, 4),
+        }
+        idx1c = maskc.idx1_dev(dev)
+        for lname, (law, xin, npar) in laws.items():
+            bps_f = 4 * (2 * d + 1 + npar * n1c)
+            bps_v = 4 * (3 * d + 1 + 2 * npar * n1c)
+            cplc = bj.Coupling((lambda l_: (lambda x2: l_))(law), maskc)
+            yc = torch.empty_like(xin)
+            kern = "bjx_coupling_affine" if lname.startswith("affine") else "bjx_coupling_chain"
+            rows.append((f"Coupling-chain {lname} [{kern}]", "chain", (lambda c_=cplc, y_=yc, x_=xin: bj.shard.with_logabsdet_jacobian_sharded(c_, x_, out=y_)), bps_f, N))
+            yin = bj.transform(cplc, xin)
+            rows.append((f"Coupling-chain inverse: {lname} [{kern}]", "chain", (lambda c_=cplc, y_=yc, x_=yin: bj.shard.with_logabsdet_jacobian_sharded(bj.inverse(c_), x_, out=y_)), bps_f, N))
+            rows.append((f"Coupling-chain vjp_params: {lname} [{kern}_vjp]", "chain", (lambda c_=cplc, x_=xin, g_=gyc, l_=lqc: bj.vjp_params(c_, x_, g_, l_)), bps_v, N))
+            if lname.startswith("affine"):
+                # the same law on the new kernels, through the C entries
+                m = I._ChainLaw(law, x, n1c, N, False)
+                ctxc = bj.context(dev)
+                libc = bj._lib.load()
+                psc = torch.empty(N, dtype=f32, device=dev)
+                xbc = torch.empty_like(x)
+                barsc = [torch.empty((N, n1c), dtype=f32, device=dev).T for _ in range(2)]
+                pbars = (C.c_void_p * 2)(*[b_.data_ptr() for b_ in barsc])
+
+                def fwd_c(inv, xi, m=m, yc=yc, psc=psc):
+                    bj._lib.check(ctxc.h, libc.bjx_coupling_chain(ctxc.h, 0, inv, I._ptr(idx1c), n1c, m.ops, m.n, m.params, m.lds, I._ptr(xi), I._ptr(yc), I._ptr(psc), None, d, N, 0), "bjx_coupling_chain")
+
+                def vjp_c(m=m):
+                    bj._lib.check(ctxc.h, libc.bjx_coupling_chain_vjp(ctxc.h, 0, 0, I._ptr(idx1c), n1c, m.ops, m.n, m.params, m.lds, I._ptr(x), I._ptr(gyc), I._ptr(lqc), I._ptr(xbc), pbars, d, N),
+                                  "bjx_coupling_chain_vjp")
+                rows.append((f"Coupling-chain {lname} [bjx_coupling_chain, one affine stage]", "chain", (lambda: fwd_c(0, x)), bps_f, N))
+                rows.append((f"Coupling-chain inverse: {lname} [bjx_coupling_chain, one affine stage]", "chain", (lambda yin=yin: fwd_c(1, yin)), bps_f, N))
+                rows.append((f"Coupling-chain vjp_params: {lname} [bjx_coupling_chain_vjp, one affine stage]", "chain", vjp_c, bps_v, N))
+
     only = [s for s in a.only.split(",") if s]
     L, ctx = bj._lib, bj.context(dev)
     lib = L.load()
