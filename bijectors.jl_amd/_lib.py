@@ -160,6 +160,16 @@ SIGNATURES_COUPLING = {
     "bjx_coupling_chain_vjp": (_i, [_vp, _i, _i, _vp, _i64, C.POINTER(BjxOp), _i, C.POINTER(_vp), C.POINTER(_i64), _vp, _vp, _vp, _vp, C.POINTER(_vp), _i64, _i64]),
 }
 
+# include/bjx_chain_vjp.h (one-pass parameter pullback of an elementwise chain): params_bar is an array of 2·n_ops pointers,
+# slot 2k + j = parameter j of stage k
+BJX_CHAIN_VJP_MAX_OPS = 4
+BJX_PLAN_CHAIN_VJP_PARAMS = 6
+SIGNATURES_CHAIN_VJP = {
+    "bjx_chain_vjp_params": (_i, [_vp, _i, C.POINTER(BjxOp), _i, _vp, _vp, _vp, _vp, C.POINTER(_vp), _i64, _i64]),
+    "bjx_plan_chain_vjp_params": (_i, [_vp, _i, C.POINTER(BjxOp), _i, _u32, _i64, C.POINTER(_vp)]),
+    "bjx_plan_run_vjp_params": (_i, [_vp, _vp, _vp, _vp, _vp, C.POINTER(_vp), _i64]),
+}
+
 _lib = None
 
 
@@ -174,10 +184,11 @@ def load() -> C.CDLL:
             "(hipcc --offload-arch=gfx950).  There is no CPU fallback."
         )
     lib = C.CDLL(LIB_PATH, mode=C.RTLD_GLOBAL)
-    missing = [n for n in list(SIGNATURES) + list(SIGNATURES_COLS) + list(SIGNATURES_COUPLING) if not hasattr(lib, n)]
+    missing = [n for n in list(SIGNATURES) + list(SIGNATURES_COLS) + list(SIGNATURES_COUPLING) + list(SIGNATURES_CHAIN_VJP) if not hasattr(lib, n)]
     if missing:  # an incomplete ABI is a build error, not something to paper over
         raise ImportError(f"{LIB_PATH} does not export {missing}; rebuild it")
-    for name, (res, args) in list(SIGNATURES.items()) + list(SIGNATURES_COLS.items()) + list(SIGNATURES_COUPLING.items()):
+    for name, (res, args) in (list(SIGNATURES.items()) + list(SIGNATURES_COLS.items()) + list(SIGNATURES_COUPLING.items())
+                              + list(SIGNATURES_CHAIN_VJP.items())):
         fn = getattr(lib, name)
         fn.restype = res
         fn.argtypes = args

@@ -8,6 +8,7 @@
 #include <thread>
 
 #include "bjx_internal.h"
+#include "../../include/bjx_chain_vjp.h"
 
 // ------------------------------------------------------------------ finalize
 // One 256-thread block sums the per-block partials in a fixed order (thread t takes
@@ -390,6 +391,29 @@ BJX_API int bjx_plan_run_vjp(bjx_plan* plan, const void* x, const void* y_bar, c
   return bjx_stacked_vjp(plan->ctx, plan->dt, plan->segs, plan->n_segs, x, y_bar, ladj_bar, x_bar, plan->dim, batch);
 }
 
+// the parameter side of the gradient path (include/bjx_chain_vjp.h): op list and wanted slots validated once, parameters by pointer
+BJX_API int bjx_plan_chain_vjp_params(bjx_ctx* ctx, bjx_dtype dt, const bjx_op* ops, int n_ops, uint32_t wanted_slots_mask, int64_t dim, bjx_plan** out) {
+  if (!ctx || !out) return BJX_ERR_ARG;
+  *out = nullptr;
+  { const int rc = bjx_chain_vjp_check(ctx, "bjx_plan_chain_vjp_params", dt, ops, n_ops, wanted_slots_mask, dim); if (rc) return rc; }
+  bjx_plan* p;
+  { const int rc = bjx_plan_new(ctx, out, &p); if (rc) return rc; }
+  p->kind = BJX_PLAN_CHAIN_VJP_PARAMS; p->dt = dt; p->n_ops = n_ops; p->dim = dim; p->wanted = wanted_slots_mask;
+  for (int k = 0; k < n_ops; ++k) p->ops[k] = ops[k];
+  *out = p;
+  return BJX_OK;
+}
+
+BJX_API int bjx_plan_run_vjp_params(bjx_plan* plan, const void* x, const void* y_bar, const void* ladj_bar, void* x_bar, void* const* params_bar, int64_t batch) {
+  if (!plan || !plan->ctx) return BJX_ERR_ARG;
+  bjx_ctx* ctx = plan->ctx;
+  BJX_REQUIRE(ctx, plan->kind == BJX_PLAN_CHAIN_VJP_PARAMS, BJX_ERR_ARG, "bjx_plan_run_vjp_params: not a parameter-pullback plan (kind %d)", plan->kind);
+  BJX_REQUIRE(ctx, params_bar || plan->wanted == 0, BJX_ERR_ARG, "bjx_plan_run_vjp_params: null params_bar, but the plan writes parameter slots");
+  for (int i = 0; i < 2 * plan->n_ops; ++i)
+    BJX_REQUIRE(ctx, !((plan->wanted >> i) & 1u) || params_bar[i], BJX_ERR_ARG, "bjx_plan_run_vjp_params: params_bar[%d] is null, but the plan writes that slot", i);
+  return bjx_chain_vjp_run(ctx, plan->dt, plan->ops, plan->n_ops, plan->wanted, x, y_bar, ladj_bar, x_bar, params_bar, plan->dim, batch);
+}
+
 BJX_API int bjx_plan_destroy(bjx_plan* plan) {
   delete plan;
   return BJX_OK;
@@ -399,6 +423,7 @@ BJX_API int bjx_plan_run(bjx_plan* plan, const void* in, void* out, void* ladj_p
   if (!plan || !plan->ctx) return BJX_ERR_ARG;
   bjx_ctx* ctx = plan->ctx;
   BJX_REQUIRE(ctx, plan->kind != BJX_PLAN_STACKED_VJP, BJX_ERR_ARG, "bjx_plan_run: a pullback plan runs through bjx_plan_run_vjp");
+  BJX_REQUIRE(ctx, plan->kind != BJX_PLAN_CHAIN_VJP_PARAMS, BJX_ERR_ARG, "bjx_plan_run: a parameter-pullback plan runs through bjx_plan_run_vjp_params");
   double* sum = ladj_sum;
   if (ladj_sum_t) {
     BJX_REQUIRE(ctx, plan->dt == BJX_F32, BJX_ERR_ARG, "bjx_plan_run: ladj_sum_t is the Float32 copy of the sum; a Float64 plan returns it in ladj_sum");

@@ -116,6 +116,7 @@ struct bjx_plan {
   uint32_t flags = 0;
   int n_segs = 0;               // BJX_PLAN_STACKED_VJP: the segment list of bjx_stacked_vjp
   bjx_segment* segs = nullptr;
+  uint32_t wanted = 0;          // BJX_PLAN_CHAIN_VJP_PARAMS: the parameter slots the run writes
   ~bjx_plan() { delete[] segs; }
 };
 
@@ -191,6 +192,12 @@ int bjx_ensure_partials(bjx_ctx* ctx, size_t n);
 // host side: launch the fixed-order reduction of per-block partials (+ constant term)
 int bjx_launch_finalize(bjx_ctx* ctx, int n_partials, double* ladj_sum, double host_const,
                         int use_dev_const, double dev_const_mult, uint32_t flags);
+
+// bjx_chain_vjp.hip (include/bjx_chain_vjp.h): validation (launches nothing) and run of the one-pass parameter pullback, shared by the
+// direct entry and the plan; `mask` bit i: params_bar[i] is written
+int bjx_chain_vjp_check(bjx_ctx* ctx, const char* name, bjx_dtype dt, const bjx_op* ops, int n_ops, uint32_t mask, int64_t dim);
+int bjx_chain_vjp_run(bjx_ctx* ctx, bjx_dtype dt, const bjx_op* ops, int n_ops, uint32_t mask, const void* x, const void* y_bar, const void* ladj_bar,
+                      void* x_bar, void* const* params_bar, int64_t dim, int64_t batch);
 
 // bjx_tall.hip: Ordered / Simplex on columns taller than the quad frames of bjx_seq.hip (G lanes per column, any height up to
 // 64 lanes x 128 bytes); *taken = false and nothing is launched when the shape is not for that kernel

@@ -3124,6 +3124,149 @@ def _vjp_params_affine_anywhere(b, x, out_bar, ladj_bar=None):
     return g, {"stages": grads}
 
 
+_VJP_PARAMS_KINDS = None
+
+
+def _stage_param_names(st):
+    """Attribute names of the stage's differentiable parameters in slot order (p0, p1) — () when `vjp_params` produces no cotangent
+    for it (parameter-free stages; inverse(Shift) / inverse(LeakyReLU), whose op carries -a / 1/α)."""
+    if isinstance(st, (Shift, Scale)):
+        return () if getattr(st, "matrix", False) else ("a",)
+    if isinstance(st, Inverse) and isinstance(st.orig, Scale):
+        return () if st.orig.matrix else ("a",)
+    if isinstance(st, Logit) or (isinstance(st, Inverse) and isinstance(st.orig, Logit)):
+        return ("a", "b")
+    if isinstance(st, LeakyReLU):
+        return ("alpha",)
+    return ()
+
+
+class _ParamsPlan(_FastPlan):
+    """A cached bjx_plan_chain_vjp_params: `slots` = [(slot, stage, name, offset, length, shape | None)] of the wanted parameter slots,
+    `total` = elements of the one buffer their cotangents are written into."""
+    __slots__ = ("slots", "total", "n_stages")
+
+
+def _vjp_params_build(owner, stages, x, dim, key):
+    def not_applicable():
+        fp = _ParamsPlan(None, _BIJ_EPOCH[0], None, None, False)
+        owner.__dict__.setdefault("_fast", {})[key] = fp
+        return fp
+
+    global _VJP_PARAMS_KINDS
+    if _VJP_PARAMS_KINDS is None:
+        _VJP_PARAMS_KINDS = {L.OP_IDENTITY, L.OP_EXP, L.OP_LOG, L.OP_SHIFT, L.OP_SCALE, L.OP_SCALE_INV, L.OP_LOGIT, L.OP_LOGIT_INV, L.OP_LEAKY_RELU, L.OP_SIGNFLIP}
+    if not stages or len(stages) > L.BJX_CHAIN_VJP_MAX_OPS:
+        return not_applicable()
+    ops = []
+    for st in stages:
+        o = _stage_ops(st)
+        if o is None or len(o) != 1 or o[0][0] not in _VJP_PARAMS_KINDS:
+            return not_applicable()
+        # the plan holds POINTERS: a tensor in the op must be the stage's own attribute, not a value derived per call
+        # (inverse(Shift) carries -a, inverse(LeakyReLU) 1/α: temporaries when the parameter is a tensor)
+        own = vars(st.orig if isinstance(st, Inverse) else st).values()
+        for p in o[0][1:]:
+            if isinstance(p, torch.Tensor) and not any(p is v for v in own):
+                return not_applicable()
+        ops.append(o[0])
+    arr = (L.BjxOp * len(ops))()
+    keep, slots, total, mask = [arr], [], 0, 0
+    for k, ((kind, p0, p1), st) in enumerate(zip(ops, stages)):
+        o = arr[k]
+        o.kind, o.param_len, o.p0, o.p1, o.v0, o.v1 = kind, 0, 0.0, 0.0, None, None
+        names = _stage_param_names(st)
+        lens = []
+        for j, p in enumerate((p0, p1)):
+            if p is None:
+                continue
+            if isinstance(p, (int, float)):
+                setattr(o, f"p{j}", float(p))
+                lens.append((j, 1, None))
+            elif isinstance(p, torch.Tensor):
+                if p.device != x.device or p.dtype != x.dtype or not p.is_contiguous() or p.dim() > 1:
+                    return not_applicable()
+                if p.numel() != 1 and p.numel() != dim:
+                    return not_applicable()
+                keep.append(p)
+                setattr(o, f"v{j}", p.data_ptr())
+                lens.append((j, p.numel(), tuple(p.shape)))
+            else:
+                return not_applicable()                          # lists / tuples are converted per call by the general path
+        if not lens:
+            continue
+        plen = max(n for _, n, _ in lens)
+        if any(shape is not None and n != plen for _, n, shape in lens):
+            return not_applicable()                              # a one-element tensor next to a per-row one
+        o.param_len = plen
+        for j, n, shape in lens:
+            if j < len(names):
+                n_out = n if shape is not None else 1
+                slots.append((2 * k + j, k, names[j], total, n_out, shape))
+                total += n_out
+                mask |= 1 << (2 * k + j)
+    if not slots:
+        return not_applicable()
+    ctx = context(x.device)
+    h = C.c_void_p()
+    L.check(ctx.h, L.load().bjx_plan_chain_vjp_params(ctx.h, _dt(x), arr, len(ops), mask, dim, C.byref(h)), "bjx_plan_chain_vjp_params")
+    fp = _ParamsPlan(h, _BIJ_EPOCH[0], keep, ctx, x.dtype == torch.float32)
+    fp.slots, fp.total, fp.n_stages = slots, total, len(stages)
+    owner.__dict__.setdefault("_fast", {})[key] = fp
+    return fp
+
+
+def _chain_vjp_params(b, stages, x, out_bar, ladj_bar):
+    """Input and parameter pullback of an elementwise chain within the fused limit in ONE pass (bjx_plan_run_vjp_params through a
+    plan kept on the bijector, like `_fast_chain_vjp`): -> (x_bar, [None | tensor | {name: tensor}] per stage), or None when the call
+    does not qualify (longer chains, TruncatedBijector, matrix Scale, inputs that are not dense 2-D, host-side parameter lists).
+    The plan lives until a parameter ATTRIBUTE is re-assigned (`_BIJ_EPOCH`); in-place updates are seen through the pointer.  A tensor
+    whose storage is swapped behind torch's back (`.data = ...`) leaves the plan with the old address, as for `_fast_chain`:
+    re-assign the attribute (`st.a = st.a`) after such a write, which bumps the epoch and rebuilds the plan."""
+    if _FAST_OFF[0] or not isinstance(b, Transform) or not isinstance(x, torch.Tensor) or not x.is_cuda or x.dim() != 2 or not isinstance(out_bar, torch.Tensor):
+        return None
+    dim, batch = x.shape
+    dt = x.dtype
+    if dim == 0 or x.stride(0) != 1 or (batch > 1 and x.stride(1) != dim) or (dt is not torch.float32 and dt is not torch.float64):
+        return None
+    if out_bar.dtype is not dt or out_bar.shape != x.shape or out_bar.device != x.device or out_bar.stride(0) != 1 or (batch > 1 and out_bar.stride(1) != dim):
+        return None
+    dev = x.device.index
+    if dev != torch._C._cuda_getDevice():
+        return None
+    if ladj_bar is not None:
+        if not isinstance(ladj_bar, torch.Tensor) or ladj_bar.dtype is not dt or ladj_bar.dim() != 1 or ladj_bar.shape[0] != batch or ladj_bar.device != x.device \
+                or (batch > 1 and ladj_bar.stride(0) != 1):
+            ladj_bar = _ladj_bar(ladj_bar, batch, x)
+    key = ("vjp_params", dt, dim, dev, torch._C._cuda_getCurrentRawStream(dev))
+    cache = b.__dict__.get("_fast")
+    fp = cache.get(key) if cache is not None else None
+    if fp is None or fp.epoch != _BIJ_EPOCH[0]:
+        fp = _vjp_params_build(b, stages, x, dim, key)
+    if fp.h is None:
+        return None
+    xb = torch.empty((batch, dim), dtype=dt, device=x.device).T
+    buf = torch.empty(fp.total, dtype=dt, device=x.device)
+    pb = (C.c_void_p * (2 * fp.n_stages))()
+    base, esz = buf.data_ptr(), buf.element_size()
+    for slot, _, _, off, _, _ in fp.slots:
+        pb[slot] = base + off * esz
+    rc = L.load().bjx_plan_run_vjp_params(fp.h, x.data_ptr(), out_bar.data_ptr(), None if ladj_bar is None else ladj_bar.data_ptr(), xb.data_ptr(), pb, batch)
+    if rc != 0:
+        L.check(fp.ctx.h, rc, "bjx_plan_run_vjp_params")
+    grads = [None] * fp.n_stages
+    for _, k, name, off, n, shape in fp.slots:
+        g = buf[off] if shape is None else buf[off:off + n].reshape(shape)
+        st = stages[k]
+        if isinstance(st, (Shift, Scale)) or (isinstance(st, Inverse) and isinstance(st.orig, Scale)):
+            grads[k] = g
+        else:
+            if grads[k] is None:
+                grads[k] = {}
+            grads[k][name] = g
+    return xb, grads
+
+
 def vjp_params(b, x, out_bar, ladj_bar=None):
     """Pullback of `with_logabsdet_jacobian(b, x)` onto the input AND the parameters of a PlanarLayer (stack):
     returns (x_bar, {"w": w_bar, "u": u_bar, "b": b_bar}) with the parameter cotangents summed over the batch and the
@@ -3137,6 +3280,9 @@ def vjp_params(b, x, out_bar, ladj_bar=None):
     a torch.nn.Module, grads["theta"] = {name: gradient} for its named_parameters() (training a flow).
     For a chain that starts with Scale and/or Shift: (z_bar, {"scale": σ̄, "shift": μ̄}) — see _vjp_params_leading_affine.
     For a chain with Scale / Shift stages anywhere else: (x_bar, {"stages": [...]}) — see _vjp_params_affine_anywhere.
+    An elementwise chain of at most four stages on a dense 2-D input, other than the mean-field head, takes ONE pass for x̄ and every
+    stage's parameters (_chain_vjp_params): {"stages": [...]} where a Logit stage gets {"a", "b"}, LeakyReLU {"alpha"},
+    inverse(Scale) a tensor; a chain made only of such stages returns {"stages": [...]} too.
     For a composition that contains flow layers / splines / BatchNorm: (x_bar, {"stages": [...]}) — see _vjp_params_composed."""
     if isinstance(b, Coupling) or (isinstance(b, Inverse) and isinstance(b.orig, Coupling)):
         inv = isinstance(b, Inverse)
@@ -3161,7 +3307,12 @@ def vjp_params(b, x, out_bar, ladj_bar=None):
         if lead < len(stages) and isinstance(stages[lead], Shift):
             lead += 1
         if lead > 0 and not any(isinstance(st, (Scale, Shift)) for st in stages[lead:]):
+            # the mean-field head keeps bjx_stacked_vjp_moments (63 % of the HBM peak at 64 x 2^22 Float32): a three-stage
+            # chain would take the one-row-per-lane form of bjx_chain_vjp_params, which has no measured figure against it yet
             return _vjp_params_leading_affine(b, x, out_bar, ladj_bar)
+        r = _chain_vjp_params(b, stages, x, out_bar, ladj_bar)            # one pass, every stage's parameters (bjx_chain_vjp_params)
+        if r is not None:
+            return r[0], {"stages": r[1]}
         return _vjp_params_affine_anywhere(b, x, out_bar, ladj_bar)
     xc, dim, batch, vec = _prep(x)
     gc, gdim, gbatch, _ = _prep(out_bar)
