@@ -170,6 +170,12 @@ SIGNATURES_CHAIN_VJP = {
     "bjx_plan_run_vjp_params": (_i, [_vp, _vp, _vp, _vp, _vp, C.POINTER(_vp), _i64]),
 }
 
+# include/bjx_radial_stack.h (a run of RadialLayers in one launch): alpha_, beta T[n_layers]; z0 T[dim, n_layers], layer 0 first
+SIGNATURES_RADIAL_STACK = {
+    "bjx_radial_stack": (_i, [_vp, _i, _i, _vp, _vp, _vp, _i, _vp, _vp] + _tail),
+    "bjx_radial_stack_vjp": (_i, [_vp, _i, _i, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _i64, _i64]),
+}
+
 _lib = None
 
 
@@ -184,11 +190,12 @@ def load() -> C.CDLL:
             "(hipcc --offload-arch=gfx950).  There is no CPU fallback."
         )
     lib = C.CDLL(LIB_PATH, mode=C.RTLD_GLOBAL)
-    missing = [n for n in list(SIGNATURES) + list(SIGNATURES_COLS) + list(SIGNATURES_COUPLING) + list(SIGNATURES_CHAIN_VJP) if not hasattr(lib, n)]
+    missing = [n for n in list(SIGNATURES) + list(SIGNATURES_COLS) + list(SIGNATURES_COUPLING) + list(SIGNATURES_CHAIN_VJP) + list(SIGNATURES_RADIAL_STACK)
+               if not hasattr(lib, n)]
     if missing:  # an incomplete ABI is a build error, not something to paper over
         raise ImportError(f"{LIB_PATH} does not export {missing}; rebuild it")
     for name, (res, args) in (list(SIGNATURES.items()) + list(SIGNATURES_COLS.items()) + list(SIGNATURES_COUPLING.items())
-                              + list(SIGNATURES_CHAIN_VJP.items())):
+                              + list(SIGNATURES_CHAIN_VJP.items()) + list(SIGNATURES_RADIAL_STACK.items())):
         fn = getattr(lib, name)
         fn.restype = res
         fn.argtypes = args

@@ -1603,25 +1603,43 @@ def _planar_kind(s) -> int:
     return 0
 
 
+def _radial_kind(s) -> int:
+    """+1: a RadialLayer stage, -1: inverse(RadialLayer), 0: anything else."""
+    if isinstance(s, RadialLayer):
+        return 1
+    if isinstance(s, Inverse) and isinstance(s.orig, RadialLayer):
+        return -1
+    return 0
+
+
 def _planned(stages):
     """The composition planner (src/bijectors/composed.jl:4-25 applies a chain stage by stage; docs/src/flows.md:115 is how the
     reference writes a flow).  `stages` in application order -> (planned stages, spans): every maximal run of PlanarLayer stages
     becomes one `_PlanarRun` (ONE bjx_planar launch over the batch instead of one per layer: 1 028 instead of 8 224 B/sample for
-    eight layers at dim 128), a run of inverse(PlanarLayer) stages the inverse of the reversed run; everything else stays.
+    eight layers at dim 128), a run of inverse(PlanarLayer) stages the inverse of the reversed run; maximal runs of >= 2 RadialLayer
+    stages become one `_RadialRun` (bjx_radial_stack) the same way; everything else — a single radial stage included — stays.
     spans[i] = (lo, hi): planned stage i covers stages[lo:hi]."""
     out, spans, i = [], [], 0
     while i < len(stages):
         kind = _planar_kind(stages[i])
+        rkind = 0 if kind else _radial_kind(stages[i])
         j = i + 1
         if kind:
             while j < len(stages) and _planar_kind(stages[j]) == kind:
+                j += 1
+        elif rkind:
+            while j < len(stages) and _radial_kind(stages[j]) == rkind:
                 j += 1
         if j - i == 1:
             out.append(stages[i])
         elif kind == 1:
             out.append(_PlanarRun(stages[i:j]))
-        else:       # inv(l_a) applied first, then inv(l_b), ... = inverse(l_a ∘ l_b ∘ ...): the forward run applies the LAST stage's layer first
+        elif kind == -1:       # inv(l_a) applied first, then inv(l_b), ... = inverse(l_a ∘ l_b ∘ ...): the forward run applies the LAST stage's layer first
             out.append(Inverse(_PlanarRun([st.orig for st in reversed(stages[i:j])])))
+        elif rkind == 1:
+            out.append(_RadialRun(stages[i:j]))
+        else:
+            out.append(Inverse(_RadialRun([st.orig for st in reversed(stages[i:j])])))
         spans.append((i, j))
         i = j
     return out, spans
@@ -1651,6 +1669,152 @@ class RadialLayer(Bijector):
 
     def _wlj_inv(self, x, per_sample, want_ladj=True):
         return self._run(x, True, per_sample, want_ladj)
+
+
+class _RadialRun(Bijector):
+    """A maximal run of >= 2 RadialLayer stages of a composition, in APPLICATION order (layers[0] first) — what the composition
+    planner hands to one bjx_radial_stack / bjx_radial_stack_vjp launch (include/bjx_radial_stack.h).  The layers keep their own
+    parameter tensors; the layer-major tables the kernel reads (alpha_, beta: [n_layers]; z_0: [dim, n_layers]) are gathered on the
+    device by bjx_pack_vectors and rebuilt when a parameter tensor changed (`_version`), was re-assigned or moved — the mechanism of
+    `_PlanarRun._tables`.  Shapes the fused entry refuses (BJX_ERR_UNSUPPORTED: columns taller than its register kernels hold,
+    tables beyond its LDS budget) are evaluated layer by layer, as before.  Parameter pullbacks are not fused: `vjp_params` of a
+    composition goes through the individual layers (`_vjp_params_composed`)."""
+
+    def __init__(self, layers):
+        layers = list(layers)
+        for l in layers:
+            if not isinstance(l, RadialLayer):
+                raise TypeError(f"_RadialRun: {l!r} is not a RadialLayer")
+        if not layers:
+            raise ValueError("_RadialRun: no layers")
+        self.layers = layers
+        self.n_layers = len(layers)
+        self._tab = None
+        self._srcs = None
+        self._bufs = {}
+        self._refused = set()
+
+    def _key(self):
+        return tuple(l._key() for l in self.layers)
+
+    def _tables(self, xc, dim):
+        """(alpha_, beta, z_0) tables of the run on xc's device: [n_layers], [n_layers], [dim, n_layers] (layer k at k·dim)."""
+        srcs = self._srcs
+        fresh = srcs is None or srcs[0] != xc.device or srcs[1] != xc.dtype
+        if not fresh:
+            for l, ent in zip(self.layers, srcs[2]):
+                for t, e in zip((l.alpha_, l.beta, l.z_0), ent):
+                    if t is not e[0] or e[0].data_ptr() != e[2]:
+                        fresh = True
+                        break
+                if fresh:
+                    break
+        if fresh:
+            per = []
+            for l in self.layers:
+                ent = []
+                for t in (l.alpha_, l.beta, l.z_0):
+                    c = _param(t, xc).reshape(-1)
+                    ent.append((t, c, t.data_ptr() if isinstance(t, torch.Tensor) else None, c.data_ptr()))
+                per.append(tuple(ent))
+            for ta, tb, tz in per:
+                if tz[1].numel() != dim:
+                    raise ValueError(f"DimensionMismatch: RadialLayer of dimension {tz[1].numel()} applied to {dim} rows")
+                if ta[1].numel() < 1 or tb[1].numel() < 1:
+                    raise ValueError("RadialLayer: alpha_ and beta must hold one value each")
+            n = self.n_layers
+            ab_ptrs = (C.c_void_p * (2 * n))(*([e[0][3] for e in per] + [e[1][3] for e in per]))
+            z_ptrs = (C.c_void_p * n)(*[e[2][3] for e in per])
+            # a host-resident / other-dtype parameter is converted by `_param` on every sighting: its device copy is a temporary, so such
+            # runs are re-read on every call (never kept)
+            stable = all(isinstance(e[k][0], torch.Tensor) and e[k][1].data_ptr() == e[k][2] for e in per for k in range(3))
+            srcs = (xc.device, xc.dtype, per, ab_ptrs, z_ptrs, dim)
+            self._srcs = srcs if stable else None
+        per, ab_ptrs, z_ptrs = srcs[2], srcs[3], srcs[4]
+        if srcs[5] != dim:
+            raise ValueError(f"DimensionMismatch: RadialLayer of dimension {srcs[5]} applied to {dim} rows")
+        n = self.n_layers
+        if _PARAM_CACHE["on"]:
+            key = (xc.device, xc.dtype, dim, _PARAM_CACHE["gen"], tuple((e[k][3], e[k][1]._version, e[k][0]._version if isinstance(e[k][0], torch.Tensor) else 0) for e in per for k in range(3)))
+            if self._tab is not None and self._tab[0] == key:
+                return self._tab[1]
+        ctx = context(xc.device)
+        bkey = (id(ctx), xc.dtype, dim)
+        buf = self._bufs.get(bkey)
+        if buf is None or _PARAM_CACHE["on"]:          # (a kept table must not be overwritten by the next gather: fresh buffers under cache_params)
+            buf = (torch.empty(2 * n, dtype=xc.dtype, device=xc.device), torch.empty(n * dim, dtype=xc.dtype, device=xc.device))
+            if not _PARAM_CACHE["on"]:
+                self._bufs = {bkey: buf}                # one (stream, dtype, dim) at a time: launches on a stream are ordered, so the next gather cannot overtake a reader
+        ab, z0 = buf
+        lib = L.load()
+        L.check(ctx.h, lib.bjx_pack_vectors(ctx.h, _dt(xc), 2 * n, ab_ptrs, 1, _ptr(ab)), "bjx_pack_vectors")
+        L.check(ctx.h, lib.bjx_pack_vectors(ctx.h, _dt(xc), n, z_ptrs, dim, _ptr(z0)), "bjx_pack_vectors")
+        tabs = (ab[:n], ab[n:], z0)
+        if _PARAM_CACHE["on"]:
+            self._tab = (key, tabs, per)
+        return tabs
+
+    def _fused_ok(self, xc, dim) -> bool:
+        """False: this (dtype, dim) goes layer by layer — the fused entry has refused it before."""
+        return (xc.dtype, dim) not in self._refused
+
+    def _stagewise(self, inv):
+        """The run as the single stages a composition would apply, in application order."""
+        return [Inverse(l) for l in reversed(self.layers)] if inv else list(self.layers)
+
+    def _run(self, x, inv, per_sample, want_ladj):
+        xc, dim, batch, vec = _prep(x)
+        y = None
+        if self._fused_ok(xc, dim):
+            a, be, z0 = self._tables(xc, dim)
+            ctx = context(xc.device)
+            y = _empty(dim, batch, xc, vec)
+            out = _Out(xc, batch, per_sample, want_ladj, ret_vector=True)
+            rc = L.load().bjx_radial_stack(ctx.h, _dt(xc), int(inv), _ptr(a), _ptr(be), _ptr(z0), self.n_layers, _ptr(xc), _ptr(y), _ptr(out.ps),
+                                           _ptr(out.sum), dim, batch, 0)
+            if rc != L.ERR_UNSUPPORTED:
+                L.check(ctx.h, rc, "bjx_radial_stack")
+                return y, (out.result(vec_scalar=vec and not per_sample) if want_ladj else None)
+            self._refused.add((xc.dtype, dim))
+        cur, total = x, None
+        for st in self._stagewise(inv):
+            cur, lj = st._wlj(cur, per_sample, want_ladj)
+            total = _add_ladj(total, lj)
+        if y is not None:                               # the refused call had taken the caller's output buffer (`_into`): the result goes there
+            y.copy_(cur)
+            cur = y
+        return cur, total
+
+    def _wlj(self, x, per_sample, want_ladj=True):
+        return self._run(x, False, per_sample, want_ladj)
+
+    def _wlj_inv(self, x, per_sample, want_ladj=True):
+        return self._run(x, True, per_sample, want_ladj)
+
+    def _vjp(self, x, out_bar, ladj_bar, inv):
+        xc, dim, batch, vec = _prep(x)
+        gc, gdim, gbatch, _ = _prep(out_bar)
+        if (gdim, gbatch) != (dim, batch) or gc.dtype != xc.dtype:
+            raise ValueError("DimensionMismatch: out_bar must have the shape and dtype of the output")
+        if self._fused_ok(xc, dim):
+            a, be, z0 = self._tables(xc, dim)
+            lb = _ladj_bar(ladj_bar, batch, xc)
+            ctx = context(xc.device)
+            xb = _empty(dim, batch, xc, vec)
+            rc = L.load().bjx_radial_stack_vjp(ctx.h, _dt(xc), int(inv), _ptr(a), _ptr(be), _ptr(z0), self.n_layers, _ptr(xc), _ptr(gc), _ptr(lb),
+                                               _ptr(xb), dim, batch)
+            if rc != L.ERR_UNSUPPORTED:
+                L.check(ctx.h, rc, "bjx_radial_stack_vjp")
+                return xb
+            self._refused.add((xc.dtype, dim))
+        pieces = self._stagewise(inv)                   # the chain rule layer by layer (as `_vjp_composed`)
+        inputs = [x]
+        for pc in pieces[:-1]:
+            inputs.append(transform(pc, inputs[-1]))
+        g = out_bar
+        for pc, xin in zip(reversed(pieces), reversed(inputs)):
+            g = vjp(pc, xin, g, ladj_bar)
+        return g
 
 
 class _BatchTag:
@@ -2830,6 +2994,8 @@ def vjp(b, x, out_bar, ladj_bar=None):
         rc = L.load().bjx_rqs_vjp(ctx.h, _dt(xc), int(inv), _ptr(w), _ptr(h), _ptr(d), int(base.widths.shape[1]), _ptr(xc), _ptr(gc), _ptr(lb), _ptr(xb), dim, batch)
         L.check(ctx.h, rc, "bjx_rqs_vjp")
         return xb
+    if isinstance(base, _RadialRun):                    # a run of RadialLayers: one bjx_radial_stack_vjp launch (layer by layer where it refuses)
+        return base._vjp(x, out_bar, ladj_bar, inv)
     if isinstance(base, RadialLayer):
         xc, dim, batch, vec = _prep(x)
         gc, gdim, gbatch, _ = _prep(out_bar)
@@ -2983,13 +3149,30 @@ def _has_own_params(st):
     return isinstance(base, (PlanarLayer, RadialLayer, RationalQuadraticSpline, InvertibleBatchNorm))
 
 
+def _radial_runs_unfused(b):
+    """`b._plan()` with every `_RadialRun` put back as its single stages: the fused radial kernels have no parameter pullback, so
+    `vjp_params` of a composition keeps going through each RadialLayer's own rule (bjx_radial_vjp_params)."""
+    stages, spans = b._plan()
+    orig = b._stages()
+    out, osp = [], []
+    for st, (lo, hi) in zip(stages, spans):
+        if isinstance(st.orig if isinstance(st, Inverse) else st, _RadialRun):
+            for j in range(lo, hi):
+                out.append(orig[j])
+                osp.append((j, j + 1))
+        else:
+            out.append(st)
+            osp.append((lo, hi))
+    return out, osp
+
+
 def _vjp_params_composed(b, x, out_bar, ladj_bar=None):
     """Input AND parameter pullback of a composition of layers (planar ∘ radial ∘ spline ∘ affine …): the chain rule of
     _vjp_composed with `vjp_params` at every stage that owns parameters (flow layers, splines, BatchNorm, Scale / Shift) and
     `vjp` at the others, on the PLANNED stages — a run of PlanarLayers is one bjx_planar_vjp_params launch, and its (w̄, ū, b̄)
     tables are handed back layer by layer.  Returns (x_bar, {"stages": [None | that stage's dictionary, ...]}) aligned with
     `b._stages()` (application order)."""
-    stages, spans = b._plan()
+    stages, spans = _radial_runs_unfused(b)
     inputs = [x]
     _BN_RECOMPUTE[0] = True
     try:
