@@ -176,6 +176,12 @@ SIGNATURES_RADIAL_STACK = {
     "bjx_radial_stack_vjp": (_i, [_vp, _i, _i, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _i64, _i64]),
 }
 
+# include/bjx_radial_stack_params.h (parameter pullback of a run of RadialLayers, one pass): the tables of bjx_radial_stack_vjp, then
+# in, out_bar, ladj_bar, in_bar (may be NULL), alpha_bar, beta_bar T[n_layers], z0_bar T[dim, n_layers]
+SIGNATURES_RADIAL_STACK_PARAMS = {
+    "bjx_radial_stack_vjp_params": (_i, [_vp, _i, _i, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64]),
+}
+
 _lib = None
 
 
@@ -191,11 +197,11 @@ def load() -> C.CDLL:
         )
     lib = C.CDLL(LIB_PATH, mode=C.RTLD_GLOBAL)
     missing = [n for n in list(SIGNATURES) + list(SIGNATURES_COLS) + list(SIGNATURES_COUPLING) + list(SIGNATURES_CHAIN_VJP) + list(SIGNATURES_RADIAL_STACK)
-               if not hasattr(lib, n)]
+               + list(SIGNATURES_RADIAL_STACK_PARAMS) if not hasattr(lib, n)]
     if missing:  # an incomplete ABI is a build error, not something to paper over
         raise ImportError(f"{LIB_PATH} does not export {missing}; rebuild it")
     for name, (res, args) in (list(SIGNATURES.items()) + list(SIGNATURES_COLS.items()) + list(SIGNATURES_COUPLING.items())
-                              + list(SIGNATURES_CHAIN_VJP.items()) + list(SIGNATURES_RADIAL_STACK.items())):
+                              + list(SIGNATURES_CHAIN_VJP.items()) + list(SIGNATURES_RADIAL_STACK.items()) + list(SIGNATURES_RADIAL_STACK_PARAMS.items())):
         fn = getattr(lib, name)
         fn.restype = res
         fn.argtypes = args

@@ -24,64 +24,7 @@ namespace {
 using namespace bjx;
 #include "bjx_flow_common.inc"
 
-constexpr size_t RS_LDS_BUDGET = 64 * 1024;      // per block: tables + (pullback) per-layer scalars; beyond it the entry refuses
-constexpr int RS_R_MAX = 8;                      // packs per lane of the group form (FLOW_R_MAX of bjx_flow.hip)
-
-template <int R> struct StackUC { static constexpr int value = R == 1 ? 4 : (R == 2 ? 2 : 1); };      // RadialUC of bjx_flow.hip
-template <int R> struct StackVjpUC { static constexpr int value = R == 1 ? 2 : 1; };                  // UC of radial_vjp_kernel
-
-__host__ __device__ inline size_t rs_round16(size_t b) { return (b + 15) / 16 * 16; }
-
-// One layer's scalars from ss = ‖in − z₀‖² (radial_kernel, same operation order): out = z₀ + gain·δ, or in + fwd_gain·δ
-template <class T, bool INV>
-__device__ __forceinline__ void rs_scalars(T ss, T alpha, T apb, T beta_hat, T dim_m1, T& gain, T& fwd_gain, T& ld) {
-  T r_fwd;                                          // ‖z − z₀‖ at the forward layer's input: the log-det is evaluated there
-  if (!INV) {
-    r_fwd = d_sqrt(ss);
-    gain = T(1) + beta_hat / (alpha + r_fwd);       // z + β̂/(α+r)(z−z0) = z0 + (1+β̂h)(z−z0)
-  } else {
-    const T gam = d_sqrt(ss);                       // compute_r :124-129
-    const T a = apb - gam;
-    const T rr = (d_sqrt(a * a + 4 * alpha * gam) - a) / 2;
-    gain = (alpha + rr) / (apb + rr);               // γ :96-101
-    r_fwd = gain * gam;
-  }
-  const T h_ = T(1) / (alpha + r_fwd);
-  ld = dim_m1 * d_log(T(1) + beta_hat * h_) + d_log(T(1) + beta_hat * h_ + beta_hat * (-(h_ * h_)) * r_fwd);   // :68-70
-  if (INV) ld = -ld;
-  fwd_gain = beta_hat / (alpha + r_fwd);
-}
-
-// The closed forms of radial_vjp_kernel at r = rr: J = a I + c δδᵀ, kl = ℓ̄ ℓ'(r)/r
-template <class T>
-__device__ __forceinline__ void rs_jac(T rr, T alpha, T bh, T dim_m1, T lb, T& a, T& c, T& kl) {
-  const T h = T(1) / (alpha + rr);
-  a = T(1) + bh * h;
-  const T rinv = rr > T(0) ? T(1) / rr : T(0);
-  c = -bh * h * h * rinv;
-  const T lr = dim_m1 * (-bh * h * h) / a + (T(-2) * bh * h * h + T(2) * bh * h * h * h * rr) / (T(1) + bh * h - bh * h * h * rr);
-  kl = lb * lr * rinv;                              // coefficient of δ from the log-det term
-}
-// out = ca · ḡ + cd · δ_in (δ_in = input − z₀ of the layer in the direction it is applied; dg = δ_inᵀḡ)
-template <class T, bool INV>
-__device__ __forceinline__ void rs_coef(T a, T c, T kl, T rr, T gain, T dg, T& ca, T& cd) {
-  if (!INV) { ca = a; cd = c * dg + kl; }
-  else {
-    // v = ḡ - kl δ;  δᵀv = gain·dg - kl r²;  out = v/a - c (δᵀv) δ / (a (a + c r²))     (Sherman–Morrison at the pre-image)
-    const T dv = gain * dg - kl * rr * rr;
-    ca = T(1) / a;
-    cd = gain * (-kl / a - c * dv / (a * (a + c * rr * rr)));
-  }
-}
-
-// softplus of the raw scalars, once per block: sc[2l] = α_l, sc[2l+1] = α_l + β̂_l; the z₀ table as it is
-template <class T>
-__device__ __forceinline__ void rs_stage_tables(const T* __restrict__ alpha_, const T* __restrict__ beta, const T* __restrict__ z0, int n_layers, int64_t dim,
-                                                T* sc, T* tab) {
-  const int ne = n_layers * (int)dim;
-  for (int i = threadIdx.x; i < ne; i += blockDim.x) tab[i] = z0[i];
-  for (int i = threadIdx.x; i < n_layers; i += blockDim.x) { sc[2 * i] = d_log1pexp(alpha_[i]); sc[2 * i + 1] = d_log1pexp(beta[i]); }   // :44-45
-}
+#include "bjx_radial_stack_common.inc"      // rs_scalars, rs_jac, rs_coef, the table staging and the geometry: shared with bjx_radial_stack_params.hip
 
 // ------------------------------------------------------------------ group form: map and inverse
 // LDS: [red: 32 bytes][sc: 2·L of T, padded to 16 bytes][tab: z₀, L·dim of T]
@@ -195,6 +138,7 @@ template <class T, int V, int R, bool INV>
 __global__ __launch_bounds__(256) void radial_stack_vjp_kernel(const T* __restrict__ alpha_, const T* __restrict__ beta, const T* __restrict__ z0, int n_layers,
                                                                const T* __restrict__ x, const T* gbar, const T* __restrict__ lbar, T* xbar, int64_t dim,
                                                                int64_t batch, int G) {
+#pragma clang fp contract(off)
   constexpr int UC = StackVjpUC<R>::value;
   constexpr int NS = INV ? 2 : 1;
   extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -247,7 +191,7 @@ __global__ __launch_bounds__(256) void radial_stack_vjp_kernel(const T* __restri
         const int64_t v = gl + (int64_t)r * G;
         if (v < nvc) {
 #pragma unroll
-          for (int j = 0; j < V; ++j) { const T dlt = zz[u][r].v[j] - z0r[r][j]; ss += dlt * dlt; }
+          for (int j = 0; j < V; ++j) { const T dlt = zz[u][r].v[j] - z0r[r][j]; ss = rs_fma(dlt, dlt, ss); }
         }
       }
       ss = group_sum_rt(ss, G);
@@ -272,8 +216,8 @@ __global__ __launch_bounds__(256) void radial_stack_vjp_kernel(const T* __restri
 #pragma unroll
             for (int j = 0; j < V; ++j) {
               const T dlt = zz[u][r].v[j] - z0r[r][j];
-              if (!INV) zz[u][r].v[j] = zz[u][r].v[j] + fwd_gain * dlt;
-              else zz[u][r].v[j] = z0r[r][j] + gain * dlt;
+              if (!INV) zz[u][r].v[j] = rs_fma(fwd_gain, dlt, zz[u][r].v[j]);
+              else zz[u][r].v[j] = rs_fma(gain, dlt, z0r[r][j]);
             }
           }
         }
@@ -309,7 +253,7 @@ __global__ __launch_bounds__(256) void radial_stack_vjp_kernel(const T* __restri
           const int64_t v = gl + (int64_t)r * G;
           if (v < nvc) {
 #pragma unroll
-            for (int j = 0; j < V; ++j) zz[u][r].v[j] = z0r[r][j] + (zz[u][r].v[j] - z0r[r][j]) * back;
+            for (int j = 0; j < V; ++j) zz[u][r].v[j] = rs_fma(zz[u][r].v[j] - z0r[r][j], back, z0r[r][j]);
           }
         }
       }
@@ -319,7 +263,7 @@ __global__ __launch_bounds__(256) void radial_stack_vjp_kernel(const T* __restri
         const int64_t v = gl + (int64_t)r * G;
         if (v < nvc) {
 #pragma unroll
-          for (int j = 0; j < V; ++j) dg += (zz[u][r].v[j] - z0r[r][j]) * gg[u][r].v[j];
+          for (int j = 0; j < V; ++j) dg = rs_fma(zz[u][r].v[j] - z0r[r][j], gg[u][r].v[j], dg);
         }
       }
       dg = group_sum_rt(dg, G);
@@ -330,7 +274,7 @@ __global__ __launch_bounds__(256) void radial_stack_vjp_kernel(const T* __restri
         const int64_t v = gl + (int64_t)r * G;
         if (v < nvc) {
 #pragma unroll
-          for (int j = 0; j < V; ++j) gg[u][r].v[j] = ca * gg[u][r].v[j] + cd * (zz[u][r].v[j] - z0r[r][j]);
+          for (int j = 0; j < V; ++j) gg[u][r].v[j] = rs_fma(cd, zz[u][r].v[j] - z0r[r][j], ca * gg[u][r].v[j]);
         }
       }
     }
@@ -351,19 +295,8 @@ __global__ __launch_bounds__(256) void radial_stack_vjp_kernel(const T* __restri
 // ------------------------------------------------------------------ walk form: ONE LANE per column (dim <= 32), map and inverse
 // The mapping of radial_walk_kernel (bjx_flow.hip): a wave takes 64 consecutive columns through a [64][P odd] LDS tile (DX > 0:
 // columns of exactly DX <= 7 rows are read and written by their lane directly), lane t keeps column t in registers and runs the
-// whole stack on it; nothing crosses lanes.  The layer table is wave-uniform: [z₀ padded with zeros to DMAX | α | α + β̂ | pad].
-template <class T, int DMAX>
-__device__ __forceinline__ void rs_walk_tables(const T* __restrict__ alpha_, const T* __restrict__ beta, const T* __restrict__ z0, int n_layers, int dim, T* tab, int lane) {
-  constexpr int LW = DMAX + 4;
-  for (int i = lane; i < n_layers * LW; i += 64) {
-    const int l = i / LW, q = i - l * LW;
-    T v = T(0);
-    if (q < DMAX) { if (q < dim) v = z0[l * dim + q]; }
-    else if (q == DMAX) v = d_log1pexp(alpha_[l]);          // :44
-    else if (q == DMAX + 1) v = d_log1pexp(beta[l]);        // α + β̂
-    tab[i] = v;
-  }
-}
+// whole stack on it; nothing crosses lanes.  The layer table is wave-uniform: [z₀ padded with zeros to DMAX | α | α + β̂ | pad]
+// (rs_walk_tables).
 template <class T, int DMAX, bool INV, int V, int DX = 0>
 __global__ __launch_bounds__(64) void radial_stack_walk_kernel(const T* __restrict__ alpha_, const T* __restrict__ beta, const T* __restrict__ z0, int n_layers,
                                                                 const T* x, T* y, T* ladj_ps, int dim, int P, int64_t batch, int accumulate, double* partials) {
@@ -440,6 +373,7 @@ template <class T, int DMAX, bool INV, int V>
 __global__ __launch_bounds__(64) void radial_stack_vjp_walk_kernel(const T* __restrict__ alpha_, const T* __restrict__ beta, const T* __restrict__ z0, int n_layers,
                                                                     const T* __restrict__ x, const T* gbar, const T* __restrict__ lbar, T* xbar, int dim, int P, int SP,
                                                                     int64_t batch) {
+#pragma clang fp contract(off)
   constexpr int NS = INV ? 2 : 1;
   constexpr int LW = DMAX + 4;
   extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -476,7 +410,7 @@ __global__ __launch_bounds__(64) void radial_stack_vjp_walk_kernel(const T* __re
       T z0v[DMAX], dz[DMAX];
       T ss = T(0);
 #pragma unroll
-      for (int r = 0; r < DMAX; ++r) { z0v[r] = tl[r]; dz[r] = z[r] - z0v[r]; ss += dz[r] * dz[r]; }
+      for (int r = 0; r < DMAX; ++r) { z0v[r] = tl[r]; dz[r] = z[r] - z0v[r]; ss = rs_fma(dz[r], dz[r], ss); }
       T gain = T(1), fwd_gain = T(0);
       if (!INV) {
         const T rr = d_sqrt(ss);
@@ -492,8 +426,8 @@ __global__ __launch_bounds__(64) void radial_stack_vjp_walk_kernel(const T* __re
       if (li + 1 < n_layers) {
 #pragma unroll
         for (int r = 0; r < DMAX; ++r) {
-          if (!INV) z[r] = z[r] + fwd_gain * dz[r];
-          else z[r] = z0v[r] + gain * dz[r];
+          if (!INV) z[r] = rs_fma(fwd_gain, dz[r], z[r]);
+          else z[r] = rs_fma(gain, dz[r], z0v[r]);
         }
       }
     }
@@ -515,15 +449,15 @@ __global__ __launch_bounds__(64) void radial_stack_vjp_walk_kernel(const T* __re
       if (li + 1 < n_layers) {
         const T back = !INV ? T(1) / a : T(1) / gain;
 #pragma unroll
-        for (int r = 0; r < DMAX; ++r) z[r] = z0v[r] + (z[r] - z0v[r]) * back;
+        for (int r = 0; r < DMAX; ++r) z[r] = rs_fma(z[r] - z0v[r], back, z0v[r]);
       }
       T dg = T(0);
 #pragma unroll
-      for (int r = 0; r < DMAX; ++r) dg += (z[r] - z0v[r]) * g[r];
+      for (int r = 0; r < DMAX; ++r) dg = rs_fma(z[r] - z0v[r], g[r], dg);
       T ca, cd;
       rs_coef<T, INV>(a, c, kl, rr, gain, dg, ca, cd);
 #pragma unroll
-      for (int r = 0; r < DMAX; ++r) g[r] = ca * g[r] + cd * (z[r] - z0v[r]);
+      for (int r = 0; r < DMAX; ++r) g[r] = rs_fma(cd, z[r] - z0v[r], ca * g[r]);
     }
 #pragma unroll
     for (int r = 0; r < DMAX; ++r) if (r < dim) mx[r] = g[r];
@@ -534,26 +468,6 @@ __global__ __launch_bounds__(64) void radial_stack_vjp_walk_kernel(const T* __re
 }
 
 // ------------------------------------------------------------------ host
-// the lanes-per-column geometry of flow_cfg (bjx_flow.hip) with partial last packs allowed; false: the column is taller than the
-// register kernels hold
-template <class T> bool rs_group_cfg(bool aligned, int64_t dim, int* V, int* G, int* R) {
-  constexpr int VW = Vec16<T>::N;
-  const bool v_ok = aligned && dim % VW == 0;
-  int v = v_ok ? VW : 1;
-  int64_t packs = dim / v;
-  if (!v_ok && dim >= 32) { v = VW; packs = (dim + VW - 1) / VW; }     // odd heights / element-aligned bases: 16-byte packs all the same
-  int g = 1;
-  while (g < 64 && g < packs) g <<= 1;
-  const int64_t need = (packs + g - 1) / g;
-  int r = 1;
-  while (r < need) r <<= 1;
-  if (r > RS_R_MAX) return false;
-  *V = v; *G = g; *R = r;
-  return true;
-}
-// the shapes radial_walk_kernel serves
-template <class T> bool rs_walk_shape(int64_t dim) { return dim <= 32 && (dim % Vec16<T>::N != 0 || sizeof(T) == 8); }
-
 #define RS_SWITCH_R(KERNEL, TT, VV, INVV, ...)                                                                            \
   switch (R) {                                                                                                            \
     case 1: hipLaunchKernelGGL((KERNEL<TT, VV, 1, INVV>), dim3((unsigned)grid), dim3(256), smem, ctx->stream, __VA_ARGS__); break;  \

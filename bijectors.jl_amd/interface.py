@@ -1677,8 +1677,9 @@ class _RadialRun(Bijector):
     parameter tensors; the layer-major tables the kernel reads (alpha_, beta: [n_layers]; z_0: [dim, n_layers]) are gathered on the
     device by bjx_pack_vectors and rebuilt when a parameter tensor changed (`_version`), was re-assigned or moved — the mechanism of
     `_PlanarRun._tables`.  Shapes the fused entry refuses (BJX_ERR_UNSUPPORTED: columns taller than its register kernels hold,
-    tables beyond its LDS budget) are evaluated layer by layer, as before.  Parameter pullbacks are not fused: `vjp_params` of a
-    composition goes through the individual layers (`_vjp_params_composed`)."""
+    tables beyond its LDS budget) are evaluated layer by layer, as before.  The parameter pullback of the run, forward and inverse,
+    is one streaming pass as well (`_vjp_params`: bjx_radial_stack_vjp_params, include/bjx_radial_stack_params.h); where that entry
+    refuses, the layers' own rules one after another."""
 
     def __init__(self, layers):
         layers = list(layers)
@@ -1815,6 +1816,41 @@ class _RadialRun(Bijector):
         for pc, xin in zip(reversed(pieces), reversed(inputs)):
             g = vjp(pc, xin, g, ladj_bar)
         return g
+
+    def _vjp_params(self, x, out_bar, ladj_bar, inv):
+        """Input AND parameter pullback of the run (inv: of its inverse) -> (x_bar, [{"alpha_", "beta", "z_0"} of layers[0], layers[1],
+        …]) — the raw parameters behind softplus, summed over the batch, in the layers' own shapes.  One streaming pass
+        (bjx_radial_stack_vjp_params) plus its folds, whatever the number of layers; a shape that entry refuses (BJX_ERR_UNSUPPORTED:
+        its Float64 accumulators come on top of the pullback's LDS tables) is remembered and goes through the single layers' rules
+        (bjx_radial_vjp_params; inverse: `_vjp_params_inverse`), as every run did before."""
+        xc, dim, batch, vec = _prep(x)
+        gc, gdim, gbatch, _ = _prep(out_bar)
+        if (gdim, gbatch) != (dim, batch) or gc.dtype != xc.dtype:
+            raise ValueError("DimensionMismatch: out_bar must have the shape and dtype of the output")
+        n = self.n_layers
+        if self._fused_ok(xc, dim) and ("params", xc.dtype, dim) not in self._refused:
+            a, be, z0 = self._tables(xc, dim)
+            lb = _ladj_bar(ladj_bar, batch, xc)
+            ctx = context(xc.device)
+            xb = _empty(dim, batch, xc, vec)
+            ab = torch.empty(2 * n, dtype=xc.dtype, device=xc.device)
+            zb = torch.empty(n * dim, dtype=xc.dtype, device=xc.device)
+            rc = L.load().bjx_radial_stack_vjp_params(ctx.h, _dt(xc), int(inv), _ptr(a), _ptr(be), _ptr(z0), n, _ptr(xc), _ptr(gc), _ptr(lb), _ptr(xb),
+                                                      _ptr(ab[:n]), _ptr(ab[n:]), _ptr(zb), dim, batch)
+            if rc != L.ERR_UNSUPPORTED:
+                L.check(ctx.h, rc, "bjx_radial_stack_vjp_params")
+                return xb, [{"alpha_": ab[k:k + 1], "beta": ab[n + k:n + k + 1], "z_0": zb[k * dim:(k + 1) * dim].reshape(_param(l.z_0, xc).shape)}
+                            for k, l in enumerate(self.layers)]
+            self._refused.add(("params", xc.dtype, dim))
+        pieces = self._stagewise(inv)                   # the chain rule layer by layer (as `_vjp_params_composed` on single stages)
+        inputs = [x]
+        for pc in pieces[:-1]:
+            inputs.append(transform(pc, inputs[-1]))
+        g, grads = out_bar, []
+        for pc, xin in zip(reversed(pieces), reversed(inputs)):
+            g, gr = vjp_params(pc, xin, g, ladj_bar)
+            grads.append(gr)
+        return g, (grads if inv else grads[::-1])       # forward: the last layer came first; inverse: pieces run from the last layer down
 
 
 class _BatchTag:
@@ -3150,8 +3186,8 @@ def _has_own_params(st):
 
 
 def _radial_runs_unfused(b):
-    """`b._plan()` with every `_RadialRun` put back as its single stages: the fused radial kernels have no parameter pullback, so
-    `vjp_params` of a composition keeps going through each RadialLayer's own rule (bjx_radial_vjp_params)."""
+    """`b._plan()` with every `_RadialRun` put back as its single stages — the stage list of the layer-by-layer parameter pullback
+    (each RadialLayer's own rule, bjx_radial_vjp_params), which `_RadialRun._vjp_params` takes where the fused entry refuses."""
     stages, spans = b._plan()
     orig = b._stages()
     out, osp = [], []
@@ -3170,9 +3206,10 @@ def _vjp_params_composed(b, x, out_bar, ladj_bar=None):
     """Input AND parameter pullback of a composition of layers (planar ∘ radial ∘ spline ∘ affine …): the chain rule of
     _vjp_composed with `vjp_params` at every stage that owns parameters (flow layers, splines, BatchNorm, Scale / Shift) and
     `vjp` at the others, on the PLANNED stages — a run of PlanarLayers is one bjx_planar_vjp_params launch, and its (w̄, ū, b̄)
-    tables are handed back layer by layer.  Returns (x_bar, {"stages": [None | that stage's dictionary, ...]}) aligned with
-    `b._stages()` (application order)."""
-    stages, spans = _radial_runs_unfused(b)
+    tables are handed back layer by layer; a run of RadialLayers (or of their inverses) is one bjx_radial_stack_vjp_params pass
+    (`_RadialRun._vjp_params`; layer by layer where that entry refuses the shape).  Returns
+    (x_bar, {"stages": [None | that stage's dictionary, ...]}) aligned with `b._stages()` (application order)."""
+    stages, spans = b._plan()
     inputs = [x]
     _BN_RECOMPUTE[0] = True
     try:
@@ -3185,7 +3222,12 @@ def _vjp_params_composed(b, x, out_bar, ladj_bar=None):
     for i in range(len(stages) - 1, -1, -1):
         st = stages[i]
         lo, hi = spans[i]
-        if _has_own_params(st) or (isinstance(st, (Scale, Shift)) and not getattr(st, "matrix", False)):
+        if isinstance(st.orig if isinstance(st, Inverse) else st, _RadialRun):
+            inv = isinstance(st, Inverse)               # layer k of the run is stage lo+k (an inverse run: stage hi-1-k)
+            g, per = (st.orig if inv else st)._vjp_params(inputs[i], g, ladj_bar, inv)
+            for k, j in enumerate(range(hi - 1, lo - 1, -1) if inv else range(lo, hi)):
+                grads[j] = per[k]
+        elif _has_own_params(st) or (isinstance(st, (Scale, Shift)) and not getattr(st, "matrix", False)):
             g, gr = vjp_params(st, inputs[i], g, ladj_bar)
             if hi - lo == 1:
                 grads[lo] = gr
@@ -3466,7 +3508,8 @@ def vjp_params(b, x, out_bar, ladj_bar=None):
     An elementwise chain of at most four stages on a dense 2-D input, other than the mean-field head, takes ONE pass for x̄ and every
     stage's parameters (_chain_vjp_params): {"stages": [...]} where a Logit stage gets {"a", "b"}, LeakyReLU {"alpha"},
     inverse(Scale) a tensor; a chain made only of such stages returns {"stages": [...]} too.
-    For a composition that contains flow layers / splines / BatchNorm: (x_bar, {"stages": [...]}) — see _vjp_params_composed."""
+    For a composition that contains flow layers / splines / BatchNorm: (x_bar, {"stages": [...]}) — see _vjp_params_composed; a run of
+    RadialLayers in it (forward or inverse) is one pass for every layer's parameters (_RadialRun._vjp_params)."""
     if isinstance(b, Coupling) or (isinstance(b, Inverse) and isinstance(b.orig, Coupling)):
         inv = isinstance(b, Inverse)
         return (b.orig if inv else b)._vjp(x, out_bar, ladj_bar, inv, params=True)
@@ -3474,6 +3517,10 @@ def vjp_params(b, x, out_bar, ladj_bar=None):
         return _vjp_params_inverse(b, x, out_bar, ladj_bar)
     if isinstance(b, RadialLayer):
         return _vjp_params_radial(b, x, out_bar, ladj_bar)
+    if isinstance(b, _RadialRun) or (isinstance(b, Inverse) and isinstance(b.orig, _RadialRun)):
+        inv = isinstance(b, Inverse)                    # {"stages": [...]} in APPLICATION order, as the composition it stands for
+        xb, per = (b.orig if inv else b)._vjp_params(x, out_bar, ladj_bar, inv)
+        return xb, {"stages": per[::-1] if inv else per}
     if isinstance(b, RationalQuadraticSpline) or (isinstance(b, Inverse) and isinstance(b.orig, RationalQuadraticSpline)):
         return _vjp_params_rqs(b, x, out_bar, ladj_bar)
     if isinstance(b, InvertibleBatchNorm):

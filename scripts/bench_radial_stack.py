@@ -1,7 +1,10 @@
-"""Fused RadialLayer run (bjx_radial_stack) against the same layers applied one by one, in one process on one GPU: forward, inverse
-and input pullback; kernel time from `bj.kernel_timed` (the hot kernels' own event pairs), median of the repeats after a warm-up.
+"""Fused RadialLayer run (bjx_radial_stack, bjx_radial_stack_vjp_params) against the same layers applied one by one, in one process on
+one GPU: forward, inverse, input pullback and parameter pullback (of the run and of its inverse); kernel time from `bj.kernel_timed`
+(the hot kernels' own event pairs), median of the repeats after a warm-up.
 The one-by-one side is what a composition cost before the planner grouped radial runs: L launches for the maps, L-1 forward
-launches plus L pullback launches for `vjp`.  Writes a markdown table (stdout and --out)."""
+launches plus L pullback launches for `vjp`; for `vjp_params` L-1 forward launches plus L single-layer parameter pullbacks with their
+reductions, and in the inverse direction three launches per layer (inverse map, inverse pullback, forward parameter pullback) and two
+negations.  Writes a markdown table (stdout and --out)."""
 import argparse
 import os
 import statistics
@@ -23,7 +26,7 @@ def med(fn, warm, reps):
     for _ in range(reps):
         _, ms, _ = bj.kernel_timed(fn)
         ts.append(ms)
-    return statistics.median(ts)
+    return statistics.median(ts), (max(ts) - min(ts)) / statistics.median(ts)
 
 
 def main():
@@ -31,11 +34,12 @@ def main():
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--reps", type=int, default=9)
     ap.add_argument("--out", default=None)
+    ap.add_argument("--ops", nargs="*", default=None, help="only these rows (forward, inverse, vjp, vjp_params, 'vjp_params inverse')")
     ap.add_argument("--log2-cap", type=int, default=None, help="cap log2(columns) (a quick run)")
     a = ap.parse_args()
     g = torch.Generator(device="cuda").manual_seed(7)
-    rows = ["| rows | layers | columns | dtype | op | fused ms | B/sample | of 8 TB/s | one by one ms | B/sample | of 8 TB/s | fused / one by one |",
-            "|---|---|---|---|---|---|---|---|---|---|---|---|"]
+    rows = ["| rows | layers | columns | dtype | op | fused ms | B/sample | of 8 TB/s | one by one ms | B/sample | of 8 TB/s | fused / one by one | spread % (max - min of the repeats, fused / one by one) |",
+            "|---|---|---|---|---|---|---|---|---|---|---|---|---|"]
     for dim, nl, lg, dt in SHAPES:
         lg = min(lg, a.log2_cap) if a.log2_cap else lg
         N, sz = 1 << lg, torch.empty(0, dtype=dt).element_size()
@@ -67,16 +71,36 @@ def main():
                 gg = bj.vjp(l, xin, gg, lb)
             return gg
 
+        def params_one_by_one(x, inverse):
+            pieces = [bj.inverse(l) for l in reversed(ls)] if inverse else ls
+            xs = [x]
+            for pc in pieces[:-1]:
+                xs.append(bj.transform(pc, xs[-1]))
+            gg, out = G, []
+            for pc, xin in zip(reversed(pieces), reversed(xs)):
+                gg, gr = bj.vjp_params(pc, xin, gg, lb)
+                out.append(gr)
+            return gg, out
+
         map_b = (2 * dim + 1) * sz
         vjp_b = (3 * dim + 1) * sz
         vjp_u = (nl - 1) * 2 * dim * sz + nl * vjp_b
+        # one layer's parameter pullback: the pullback pass, (r, δᵀȳ) written and read back with ℓ̄; its inverse: the inverse map, the
+        # inverse pullback and the negations of ȳ and ℓ̄ before it
+        par_l = vjp_b + 5 * sz
+        par_u = (nl - 1) * 2 * dim * sz + nl * par_l
+        par_ui = (nl - 1) * 2 * dim * sz + nl * (2 * dim * sz + vjp_b + (2 * dim + 2) * sz + par_l)
         for op, fused, unfused, fb, ub in (
                 ("forward", lambda: bj.with_logabsdet_jacobian(flow, Z, per_sample=True), lambda: one_by_one(Z, False), map_b, nl * map_b),
                 ("inverse", lambda: bj.with_logabsdet_jacobian(inv, Y, per_sample=True), lambda: one_by_one(Y, True), map_b, nl * map_b),
-                ("vjp", lambda: bj.vjp(flow, Z, G, lb), vjp_one_by_one, vjp_b, vjp_u)):
-            tf, tu = med(fused, a.warmup, a.reps), med(unfused, a.warmup, a.reps)
+                ("vjp", lambda: bj.vjp(flow, Z, G, lb), vjp_one_by_one, vjp_b, vjp_u),
+                ("vjp_params", lambda: bj.vjp_params(flow, Z, G, lb), lambda: params_one_by_one(Z, False), vjp_b, par_u),
+                ("vjp_params inverse", lambda: bj.vjp_params(inv, Y, G, lb), lambda: params_one_by_one(Y, True), vjp_b, par_ui)):
+            if a.ops and op not in a.ops:
+                continue
+            (tf, sf), (tu, su) = med(fused, a.warmup, a.reps), med(unfused, a.warmup, a.reps)
             rows.append(f"| {dim} | {nl} | 2^{lg} | {str(dt).split('.')[-1]} | {op} | {tf:.3f} | {fb} | {fb * N / (tf * 1e-3) / PEAK:.2f} | {tu:.3f} | {ub} | "
-                        f"{ub * N / (tu * 1e-3) / PEAK:.2f} | {tf / tu:.2f} |")
+                        f"{ub * N / (tu * 1e-3) / PEAK:.2f} | {tf / tu:.2f} | {100 * sf:.1f} / {100 * su:.1f} |")
             print(rows[-1], flush=True)
         del Z, G, Y, lb
         torch.cuda.empty_cache()
