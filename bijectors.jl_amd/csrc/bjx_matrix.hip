@@ -1416,6 +1416,7 @@ int scale_matrix_impl(bjx_ctx* ctx, int inverse, const T* a, const T* in, T* out
     // call: ~0.2 s at 1024, minutes at 8192 (a launch that long looks like a hang).  Larger systems belong to a blocked LU (rocSOLVER).
     BJX_REQUIRE(ctx, dim <= 1024, BJX_ERR_UNSUPPORTED, "bjx_scale_matrix: dim = %lld: the general-size path stops at 1024 (single-block O(dim^3) factorisation per call)", (long long)dim);
     BJX_REQUIRE(ctx, !(flags & BJX_BASE_STDNORMAL), BJX_ERR_UNSUPPORTED, "bjx_scale_matrix: BJX_BASE_STDNORMAL is served by the matrix-core kernel only (dim <= 128)");
+    BJX_REQUIRE(ctx, !pre, BJX_ERR_UNSUPPORTED, "bjx_scale_matrix_chain: served by the matrix-core kernel only (dim <= 128): the general-size path applies no chain");
     { int rc = bjx_ensure_big_ws(ctx, (size_t)dim * 2 * dim * sizeof(T)); if (rc) return rc; }
     T* Wb = reinterpret_cast<T*>(ctx->big_ws);
     double* ladb = ctx->consts + 2;
@@ -1440,6 +1441,15 @@ int scale_matrix_impl(bjx_ctx* ctx, int inverse, const T* a, const T* in, T* out
       BJX_CHECK_LAUNCH(ctx);
     }
     return BJX_OK;
+  }
+  static const int use_mfma = getenv("BJX_SCALE_MFMA") ? atoi(getenv("BJX_SCALE_MFMA")) : 1;
+  const int nrb_ = (int)((dim + 15) / 16);
+  const size_t smem_try = ((size_t)(16 * nrb_) * (16 * nrb_) + (size_t)4 * 16 * (16 * nrb_ + 4)) * sizeof(T);
+  if (pre && batch > 0) {
+    // the chain in front is applied by the matrix-core kernel's 16-byte staging only; refused BEFORE the factorisation: nothing is launched
+    constexpr int VWh = 16 / (int)sizeof(T);
+    BJX_REQUIRE(ctx, use_mfma && smem_try + 512 + (size_t)4 * 16 * nrb_ * sizeof(T) <= BJX_LDS_MAX && dim % VWh == 0 && bjx_aligned16(in) && (!out || bjx_aligned16(out)), BJX_ERR_UNSUPPORTED,
+                "bjx_scale_matrix_chain: served by the matrix-core kernel only (Float32 dim <= 128, Float64 dim <= 112, a whole number of 16-byte packs, arrays on 16-byte boundaries)");
   }
   T* W = reinterpret_cast<T*>(ctx->scratch);
   double* lad = ctx->consts + 2;
@@ -1500,15 +1510,6 @@ int scale_matrix_impl(bjx_ctx* ctx, int inverse, const T* a, const T* in, T* out
     const T* M = inverse ? W + dim : a;
     const int ldm = inverse ? (int)(2 * dim) : 0;
     BjxProf prof_(ctx);
-    static const int use_mfma = getenv("BJX_SCALE_MFMA") ? atoi(getenv("BJX_SCALE_MFMA")) : 1;
-    const int nrb_ = (int)((dim + 15) / 16);
-    const size_t smem_try = ((size_t)(16 * nrb_) * (16 * nrb_) + (size_t)4 * 16 * (16 * nrb_ + 4)) * sizeof(T);
-    if (pre) {
-      // the chain in front is applied by the matrix-core kernel's 16-byte staging only
-      constexpr int VWh = 16 / (int)sizeof(T);
-      BJX_REQUIRE(ctx, use_mfma && smem_try + 512 + (size_t)4 * 16 * nrb_ * sizeof(T) <= BJX_LDS_MAX && dim % VWh == 0 && bjx_aligned16(in) && (!out || bjx_aligned16(out)), BJX_ERR_UNSUPPORTED,
-                  "bjx_scale_matrix_chain: served by the matrix-core kernel only (dim <= 128 and a whole number of 16-byte packs, arrays on 16-byte boundaries)");
-    }
     if (use_mfma && smem_try <= BJX_LDS_MAX) {
       if (inverse && want_ladj) hipLaunchKernelGGL(scale_matrix_sum_kernel, dim3(1), dim3(1), 0, ctx->stream, lad, -1.0, lad, 0);
       const int nrb = (int)((dim + 15) / 16), DP = 16 * nrb;

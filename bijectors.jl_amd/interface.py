@@ -3939,7 +3939,8 @@ def _merge_affine_tail(d, ops, y):
 
 
 def _logpdf_full_cov_fused(d, ib, y):
-    """Full-covariance base, fusable inverse transform, dim <= 128: ONE launch when the inverse is at most three stages of exp / log / Shift /
+    """Full-covariance base, fusable inverse transform, dim <= 128 (Float64: the fused launches stop at 112 rows, BJX_ERR_UNSUPPORTED
+    beyond sends the call down the next path): ONE launch when the inverse is at most three stages of exp / log / Shift /
     Scale / Scale⁻¹ (bjx_scale_matrix_chain, round 6); else (round 5) TWO launches and three array passes instead of four
     launches and five passes — the inverse chain with the shift −μ appended writes x − μ and its per-column log-det, then the matrix
     `Scale` kernel whitens with L⁻¹ and accumulates log N(z; 0, I) − logabsdet L per column while the whitened tile is still in LDS

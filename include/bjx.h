@@ -254,7 +254,9 @@ int bjx_pd_vec_vjp(bjx_ctx* ctx, bjx_dtype dt, int inverse, const void* in, cons
  * column-major, dim <= 128.  logabsdetjac = logabsdet(a) (negated for the inverse): ladj_ps[n] holds it for every column;
  * ladj_sum = batch * logabsdet(a), or logabsdet(a) ONCE with BJX_REF_VECTOR_SCALE_LADJ — the value the reference returns
  * for a matrix of columns (:36).  The LU (partial pivoting) behind logabsdet / the inverse runs on the device per call (kept per
- * BJX_OPT_PARAM_EPOCH).  BJX_BASE_STDNORMAL (dim <= 128, ladj_ps only, out may be NULL): ladj_ps[n] additionally receives
+ * BJX_OPT_PARAM_EPOCH).  BJX_BASE_STDNORMAL (Float32: dim <= 128, Float64: dim <= 112 — the matrix padded to whole blocks of 16 rows and
+ * four 16-column tiles share the 160 KiB LDS tile, Float64 at 113 ... 128 rows does not fit: BJX_ERR_UNSUPPORTED; ladj_ps only, out may be
+ * NULL): ladj_ps[n] additionally receives
  * log N(out[:, n]; 0, I) — with inverse = 1 and a = the Cholesky factor L of a covariance, one launch turns x - mu into the
  * full-covariance normal log-density without storing the whitened values (src/transformed_distribution.jl:164-169). */
 int bjx_scale_matrix(bjx_ctx* ctx, bjx_dtype dt, int inverse, const void* a, const void* in, void* out,
@@ -265,8 +267,12 @@ int bjx_scale_matrix(bjx_ctx* ctx, bjx_dtype dt, int inverse, const void* a, con
  * applied to every element as its tile is loaded.  Served stages: BJX_OP_EXP, BJX_OP_LOG, BJX_OP_SHIFT, BJX_OP_SCALE, BJX_OP_SCALE_INV with a host scalar
  * (param_len 1, p0) or one value per row (param_len == dim, v0); n_ops <= 4.  ladj_ps[n] = logabsdetjac of c at column n + logabsdet(a)
  * (negated for the inverse) (+ log N(out[:, n]; 0, I) with BJX_BASE_STDNORMAL; added to its content with BJX_ACCUMULATE); out may be
- * NULL when ladj_ps is wanted alone.  BJX_ERR_UNSUPPORTED (nothing launched) for any other stage, for dim > 128 or not a whole number
- * of 16-byte packs, for arrays off 16-byte boundaries and with BJX_SCALE_MFMA=0: the caller then runs bjx_chain and bjx_scale_matrix. */
+ * NULL when ladj_ps is wanted alone.  Served sizes: Float32 up to 128 rows, Float64 up to 112 rows (the 160 KiB LDS tile holds the matrix
+ * padded to whole blocks of 16 rows, four 16-column tiles and the stage tables: Float64 at 112 rows fills it exactly).
+ * BJX_ERR_UNSUPPORTED (nothing launched, nothing written) for any other stage, a scalar parameter on the device, n_ops > 4, for more rows
+ * than that or not a whole number of 16-byte packs, for `in` / `out` off 16-byte boundaries and with BJX_SCALE_MFMA=0: the caller then runs
+ * bjx_chain and bjx_scale_matrix.  The same call on the same arguments gives the same bits (a column's log-det parts are added by the lanes
+ * of ONE wave, in registers or by that wave's LDS adds in lane order). */
 int bjx_scale_matrix_chain(bjx_ctx* ctx, bjx_dtype dt, int inverse, const void* a, const bjx_op* ops, int n_ops, const void* in,
                            void* out, void* ladj_ps, int64_t dim, int64_t batch, uint32_t flags);
 /* Parameter pullback of the matrix Scale (ext/BijectorsReverseDiffExt.jl:72-115; scale.jl:14,17,35-36):

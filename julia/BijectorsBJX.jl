@@ -1612,7 +1612,7 @@ end
 # bjx_scale_matrix_chain (include/bjx.h): `pre` (at most four stages of exp / log / Shift / Scale — the inverse of the transform and the shift
 # by the mean) applied to each tile of `y` as the matrix-core kernel loads it, whitening by L⁻¹ and log N(z; 0, I) − logabsdet L per column
 # while the tile is in LDS: src/transformed_distribution.jl:164-169 in one pass over y.  `nothing` when the library answers
-# BJX_ERR_UNSUPPORTED (other stages, dim > 128 or not whole 16-byte packs, BJX_SCALE_MFMA=0): the caller runs bjx_chain + bjx_scale_matrix.
+# BJX_ERR_UNSUPPORTED (other stages, more than 128 Float32 / 112 Float64 rows or not whole 16-byte packs, BJX_SCALE_MFMA=0): the caller runs bjx_chain + bjx_scale_matrix.
 function full_cov_logpdf_fused(Lc::ROCMatrix{T}, pre::Vector{BjxOp}, y::ROCMatrix{T}, keep) where {T<:BjxFloat}
     (length(pre) <= 4 && all(o -> o.kind in (Int32(OP_EXP), Int32(OP_LOG), Int32(OP_SHIFT), Int32(OP_SCALE), Int32(OP_SCALE_INV)), pre)) || return nothing
     d, n = size(y); lp = similar(y, T, n)
