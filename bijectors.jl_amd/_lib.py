@@ -182,6 +182,13 @@ SIGNATURES_RADIAL_STACK_PARAMS = {
     "bjx_radial_stack_vjp_params": (_i, [_vp, _i, _i, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64]),
 }
 
+# include/bjx_radial_stack_logpdf.h (log-density of a flow of RadialLayers over a normal base, with all its cotangents, one pass): the
+# tables, mu, sigma (may be NULL), y, lp_bar (may be NULL), lp_ps, lp_sum (device double), y_bar, alpha_bar, beta_bar, z0_bar, mu_bar,
+# sigma_bar (every output may be NULL; the three layer cotangents together)
+SIGNATURES_RADIAL_STACK_LOGPDF = {
+    "bjx_radial_stack_logpdf_vjp_params": (_i, [_vp, _i, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64]),
+}
+
 _lib = None
 
 
@@ -197,11 +204,12 @@ def load() -> C.CDLL:
         )
     lib = C.CDLL(LIB_PATH, mode=C.RTLD_GLOBAL)
     missing = [n for n in list(SIGNATURES) + list(SIGNATURES_COLS) + list(SIGNATURES_COUPLING) + list(SIGNATURES_CHAIN_VJP) + list(SIGNATURES_RADIAL_STACK)
-               + list(SIGNATURES_RADIAL_STACK_PARAMS) if not hasattr(lib, n)]
+               + list(SIGNATURES_RADIAL_STACK_PARAMS) + list(SIGNATURES_RADIAL_STACK_LOGPDF) if not hasattr(lib, n)]
     if missing:  # an incomplete ABI is a build error, not something to paper over
         raise ImportError(f"{LIB_PATH} does not export {missing}; rebuild it")
     for name, (res, args) in (list(SIGNATURES.items()) + list(SIGNATURES_COLS.items()) + list(SIGNATURES_COUPLING.items())
-                              + list(SIGNATURES_CHAIN_VJP.items()) + list(SIGNATURES_RADIAL_STACK.items()) + list(SIGNATURES_RADIAL_STACK_PARAMS.items())):
+                              + list(SIGNATURES_CHAIN_VJP.items()) + list(SIGNATURES_RADIAL_STACK.items()) + list(SIGNATURES_RADIAL_STACK_PARAMS.items())
+                              + list(SIGNATURES_RADIAL_STACK_LOGPDF.items())):
         fn = getattr(lib, name)
         fn.restype = res
         fn.argtypes = args

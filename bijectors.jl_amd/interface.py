@@ -33,7 +33,7 @@ __all__ = [
     "VecCholeskyBijector", "VecCorrBijector", "CorrBijector", "PDBijector", "PDVecBijector", "Permute", "PlanarLayer", "RadialLayer", "InvertibleBatchNorm", "RationalQuadraticSpline",
     "PartitionMask", "Coupling", "Stacked", "NamedStacked", "Columnwise", "columnwise", "vjp", "istraining", "training", "transform", "inverse", "logabsdetjac", "with_logabsdet_jacobian",
     "with_logabsdet_jacobian_", "transform_", "output_size", "isinvertible", "isclosedform", "colmajor", "context", "_fast_plans",
-    "PlanarResult", "vjp_params", "row_moments", "MvNormal", "TorchBase", "TransformedDistribution", "transformed", "logpdf", "rand",
+    "PlanarResult", "vjp_params", "row_moments", "MvNormal", "TorchBase", "TransformedDistribution", "transformed", "logpdf", "logpdf_vjp_params", "rand",
     "CapturedStep", "kernel_timed", "cache_params", "invalidate_params",
 ]
 
@@ -4030,6 +4030,158 @@ def logpdf(td: TransformedDistribution, y, reference_shape: bool = False):
         return pl._run(y, True, True, True, flags=L.BJX_BASE_STDNORMAL, store=False)[1]
     x, lj = ib._wlj(y, per_sample=True)
     return _run_chain(base, x, True, True, store=False)[1] + lj
+
+
+# ------------------------------------------------------------------ log-density of a transformed distribution, value AND gradients
+_PARAM_STAGES = ("PlanarLayer", "_PlanarRun", "RadialLayer", "_RadialRun", "RationalQuadraticSpline", "InvertibleBatchNorm", "Coupling", "Scale", "Shift", "Logit",
+                 "LeakyReLU")
+
+
+def _td_inverse(td):
+    """inverse(td.transform), kept on the distribution while the transform is the same object and no bijector attribute was re-assigned
+    (the planner's `_RadialRun` — its gathered tables and the shapes the fused entries refused — lives on the inverse composition)."""
+    hit = td.__dict__.get("_inv_cache")
+    if hit is None or hit[0] is not td.transform or hit[1] != _BIJ_EPOCH[0]:
+        hit = (td.transform, _BIJ_EPOCH[0], inverse(td.transform))
+        td.__dict__["_inv_cache"] = hit
+    return hit[2]
+
+
+def _logpdf_grad_run(ib):
+    """(run, single) when the plan of `ib` is one inverse(_RadialRun) — or one inverse(RadialLayer), a stack of one kept on the layer —,
+    else None."""
+    st = ib
+    if isinstance(ib, ComposedFunction):
+        plan = ib._plan()[0]
+        if len(plan) != 1:
+            return None
+        st = plan[0]
+    if not isinstance(st, Inverse):
+        return None
+    if isinstance(st.orig, _RadialRun):
+        return st.orig, False
+    if type(st.orig) is RadialLayer:
+        run = st.orig.__dict__.get("_stack_of_one")
+        if run is None:
+            run = _RadialRun([st.orig])
+            st.orig.__dict__["_stack_of_one"] = run
+        return run, True
+    return None
+
+
+def _has_param_stage(ib) -> bool:
+    stages = ib._stages() if isinstance(ib, ComposedFunction) else [ib]
+    return any(type(st.orig if isinstance(st, Inverse) else st).__name__ in _PARAM_STAGES for st in stages)
+
+
+def _logpdf_grad_fused(run, single, d, yc, dim, batch, vec, lp_bar, params, want_y_bar):
+    """One call of bjx_radial_stack_logpdf_vjp_params (include/bjx_radial_stack_logpdf.h); None when the entry refuses the shape."""
+    n = run.n_layers
+    a, be, z0 = run._tables(yc, dim)
+    mu = None if d.mu is None else _param(d.mu, yc).reshape(-1)
+    sigma = None if d.sigma is None else _param(d.sigma, yc).reshape(-1)
+    lb = _ladj_bar(lp_bar, batch, yc)
+    ctx = context(yc.device)
+    lp = torch.empty(batch, dtype=yc.dtype, device=yc.device)
+    yb = _empty(dim, batch, yc, vec) if want_y_bar else None
+    ab = zb = mb = sb = None
+    if params:
+        ab = torch.empty(2 * n, dtype=yc.dtype, device=yc.device)
+        zb = torch.empty(n * dim, dtype=yc.dtype, device=yc.device)
+        mb = None if mu is None else torch.empty(dim, dtype=yc.dtype, device=yc.device)
+        sb = None if sigma is None else torch.empty(dim, dtype=yc.dtype, device=yc.device)
+    rc = L.load().bjx_radial_stack_logpdf_vjp_params(ctx.h, _dt(yc), _ptr(a), _ptr(be), _ptr(z0), n, _ptr(mu), _ptr(sigma), _ptr(yc), _ptr(lb), _ptr(lp), None, _ptr(yb),
+                                                     _ptr(ab[:n]) if params else None, _ptr(ab[n:]) if params else None, _ptr(zb), _ptr(mb), _ptr(sb), dim, batch)
+    if rc == L.ERR_UNSUPPORTED:
+        return None
+    L.check(ctx.h, rc, "bjx_radial_stack_logpdf_vjp_params")
+    if not params:
+        return lp, yb, {}
+    per = [{"alpha_": ab[k:k + 1], "beta": ab[n + k:n + k + 1], "z_0": zb[k * dim:(k + 1) * dim].reshape(_param(l.z_0, yc).shape)} for k, l in enumerate(run.layers)]
+    base = {}
+    if mb is not None:
+        base["mu"] = mb
+    if sb is not None:
+        base["sigma"] = sb
+    return lp, yb, {"transform": per[0] if single else {"stages": per[::-1]}, "base": base}       # stage j of inverse(run) is inverse(layer L-1-j)
+
+
+def logpdf_vjp_params(td: TransformedDistribution, y, lp_bar=None, params=True, want_y_bar=True):
+    """Value and gradients of `logpdf(td, y)` (the reference differentiates src/transformed_distribution.jl:164-169): the per-column
+    log-density lp, the cotangent of y and — the step maximum-likelihood training of a flow takes — the cotangents of the
+    transform's and the base's parameters, for the cotangent c = `lp_bar` of lp (None = 1, a number, or a (batch,) tensor; the
+    conventions of `ladj_bar`).  -> (lp, y_bar, grads).
+
+    With x = f⁻¹(y), w = (x − μ)/σ and ℓ = logabsdetjac(inverse(f), y): lp = −½‖w‖² − Σ log σ − (d/2) log 2π + ℓ; x̄ = −c·w/σ, ℓ̄ = c;
+    (ȳ, θ̄) is the pullback of with_logabsdet_jacobian(inverse(f), ·) at y; μ̄ = Σ c·w/σ, σ̄ = Σ c·(w² − 1)/σ.
+    grads = {"transform": what `vjp_params(inverse(td.transform), y, x̄, c)` returns second ({} for a transform without parameters),
+    "base": {"mu": μ̄, "sigma": σ̄}} (those the base has); params=False: grads = {} and only the input pullback runs (a flow-shaped
+    HMC target).  y_bar is None with want_y_bar=False.  The base is an `MvNormal`, standard or diagonal.
+
+    A flow that is a run of RadialLayers (or one RadialLayer) on a dense input takes ONE streaming pass over y
+    (bjx_radial_stack_logpdf_vjp_params: the inverse sweep, the base density and the reverse sweep on the resident column) plus its
+    folds; shapes that entry refuses are remembered (per dtype, dim and whether μ̄ / σ̄ are asked for) and, like every other transform, go through `_preimage`, the arithmetic above
+    and `vjp_params` / `vjp` of the inverse."""
+    d = td.dist
+    if not isinstance(d, MvNormal):
+        raise NotImplementedError("logpdf_vjp_params: the base must be an MvNormal (standard or diagonal); other bases are not differentiated")
+    if getattr(d, "scale_tril", None) is not None:
+        raise NotImplementedError("logpdf_vjp_params: a full-covariance MvNormal base is not differentiated (diagonal or standard only)")
+    rows = y.shape[0] if isinstance(y, torch.Tensor) and y.dim() >= 1 else None
+    for name, p in (("mu", d.mu), ("sigma", d.sigma)):     # both paths read `dim` entries of each: checked before anything reaches a kernel
+        if p is not None and p.numel() != rows:
+            raise ValueError(f"DimensionMismatch: base parameter {name} of length {p.numel()} for {rows} rows")
+    ib = _td_inverse(td)
+    yc, dim, batch, vec = _prep(y)
+    if d.dim != dim:
+        raise ValueError(f"DimensionMismatch: a base of dimension {d.dim} for {dim} rows")
+    hit = None if ib is identity else _logpdf_grad_run(ib)
+    if hit is not None and _colmajor_dense(y):
+        run, single = hit
+        # what the entry refuses depends on whether the rows of μ̄ / σ̄ widen its tables: remembered per (dtype, dim, those rows asked for)
+        key = ("logpdf", yc.dtype, dim, bool(params and (d.mu is not None or d.sigma is not None)))
+        if run._fused_ok(yc, dim) and key not in run._refused:
+            r = _logpdf_grad_fused(run, single, d, yc, dim, batch, vec, lp_bar, params, want_y_bar)
+            if r is not None:
+                return r
+            run._refused.add(key)
+    # ---- any transform: the pre-image, the base terms (sums over the batch in Float64), then the inverse's own pullback
+    x, lj = _preimage(ib, y)
+    x2 = _prep(x)[0].reshape(dim, batch) if vec else _prep(x)[0]
+    c = _ladj_bar(1.0 if lp_bar is None else lp_bar, batch, yc)
+    mu = None if d.mu is None else _param(d.mu, yc).reshape(-1, 1)
+    sigma = None if d.sigma is None else _param(d.sigma, yc).reshape(-1, 1)
+    w = x2 if mu is None else x2 - mu
+    if sigma is not None:
+        w = w / sigma
+    cst = 0.5 * dim * math.log(2.0 * math.pi)
+    lp = -0.5 * (w * w).sum(dim=0) - cst
+    if sigma is not None:
+        lp = lp - torch.log(sigma.to(torch.float64)).sum().to(yc.dtype)
+    if lj is not None:
+        lp = lp + lj.reshape(-1)
+    mg = w * c.reshape(1, -1)                               # c·w, then c·w/σ = −x̄
+    if sigma is not None:
+        mg = mg / sigma
+    xb = -mg
+    xb = xb.reshape(dim) if vec else colmajor(xb)
+    if ib is identity:
+        yb, G = xb, {}
+    elif params and _has_param_stage(ib):
+        yb, G = vjp_params(ib, y, xb, c)
+    else:
+        yb, G = vjp(ib, y, xb, c), {}
+    if not want_y_bar:
+        yb = None
+    if not params:
+        return lp, yb, {}
+    base = {}
+    if mu is not None:
+        base["mu"] = mg.to(torch.float64).sum(dim=1).to(yc.dtype)
+    if sigma is not None:
+        s64 = sigma.to(torch.float64).reshape(-1)
+        base["sigma"] = ((mg * w).to(torch.float64).sum(dim=1) - c.to(torch.float64).sum() / s64).to(yc.dtype)
+    return lp, yb, {"transform": G, "base": base}
 
 
 def rand(td: TransformedDistribution, n: int, seed: int = 0, device=None, dtype=torch.float32, col0: int = 0, fused: bool = True):
