@@ -189,6 +189,13 @@ SIGNATURES_RADIAL_STACK_LOGPDF = {
     "bjx_radial_stack_logpdf_vjp_params": (_i, [_vp, _i, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64]),
 }
 
+# include/bjx_planar_logpdf.h (log-density of a flow of PlanarLayers over a normal base, with all its cotangents): the layer-major
+# tables w, u, b, n_layers, mu, sigma (may be NULL), y, lp_bar (may be NULL), lp_ps, y_bar, w_bar, u_bar, b_bar, mu_bar, sigma_bar (every
+# output may be NULL; the three layer cotangents together), work (caller-owned scratch, NULL when nothing is summed over the batch)
+SIGNATURES_PLANAR_LOGPDF = {
+    "bjx_planar_logpdf_vjp_params": (_i, [_vp, _i, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64]),
+}
+
 _lib = None
 
 
@@ -204,12 +211,12 @@ def load() -> C.CDLL:
         )
     lib = C.CDLL(LIB_PATH, mode=C.RTLD_GLOBAL)
     missing = [n for n in list(SIGNATURES) + list(SIGNATURES_COLS) + list(SIGNATURES_COUPLING) + list(SIGNATURES_CHAIN_VJP) + list(SIGNATURES_RADIAL_STACK)
-               + list(SIGNATURES_RADIAL_STACK_PARAMS) + list(SIGNATURES_RADIAL_STACK_LOGPDF) if not hasattr(lib, n)]
+               + list(SIGNATURES_RADIAL_STACK_PARAMS) + list(SIGNATURES_RADIAL_STACK_LOGPDF) + list(SIGNATURES_PLANAR_LOGPDF) if not hasattr(lib, n)]
     if missing:  # an incomplete ABI is a build error, not something to paper over
         raise ImportError(f"{LIB_PATH} does not export {missing}; rebuild it")
     for name, (res, args) in (list(SIGNATURES.items()) + list(SIGNATURES_COLS.items()) + list(SIGNATURES_COUPLING.items())
                               + list(SIGNATURES_CHAIN_VJP.items()) + list(SIGNATURES_RADIAL_STACK.items()) + list(SIGNATURES_RADIAL_STACK_PARAMS.items())
-                              + list(SIGNATURES_RADIAL_STACK_LOGPDF.items())):
+                              + list(SIGNATURES_RADIAL_STACK_LOGPDF.items()) + list(SIGNATURES_PLANAR_LOGPDF.items())):
         fn = getattr(lib, name)
         fn.restype = res
         fn.argtypes = args

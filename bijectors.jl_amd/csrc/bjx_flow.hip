@@ -3246,17 +3246,12 @@ __global__ __launch_bounds__(256) void planar_param_finalize_kernel(const double
   if (threadIdx.x == 0) b_bar[k] = (T)bsum;
 }
 
+// The reduction stage of the parameter pullback: (w̄, ū, b̄) from the column Z₀ = `in`, the output cotangent, ℓ̄ and the per-layer
+// (s̄, t) tables [batch][nl] a pullback sweep left, with the û [nl][dim] / wᵀû [nl] tables.  Jointly linear in (out_bar, ladj_bar, s̄).
+// Called by planar_vjp_params_impl below and — through bjx::planar_param_reduce_launch — by bjx_planar_logpdf.hip.
 template <class T>
-int planar_vjp_params_impl(bjx_ctx* ctx, const T* w, const T* u, const T* b, int nl, const T* in, const T* out_bar, const T* ladj_bar, T* in_bar,
-                           T* w_bar, T* u_bar, T* b_bar, T* work, int64_t dim, int64_t batch) {
-  BJX_REQUIRE(ctx, batch >= 1, BJX_ERR_SHAPE, "bjx_planar_vjp_params: empty batch");
-  T* s_out = work;                                   // [nl, batch]
-  T* t_out = work + (size_t)nl * batch;
-  int rc = planar_vjp_impl<T>(ctx, 0, w, u, b, nl, in, out_bar, ladj_bar, in_bar, dim, batch, t_out, s_out);
-  if (rc) return rc;
-  // tables left by planar_vjp_impl: û [nl][dim], wᵀû [nl] — in the scratch, or (a stack too large for it) at the head of the grown workspace
-  const T* u_hat = (((size_t)nl * dim + nl) * sizeof(T) + 255) / 256 * 256 > BJX_SCRATCH_BYTES ? static_cast<const T*>(ctx->big_ws) : static_cast<const T*>(ctx->scratch);
-  const T* wtu = u_hat + (size_t)nl * dim;
+int planar_param_reduce_impl(bjx_ctx* ctx, const T* w, const T* u, int nl, const T* in, const T* out_bar, const T* ladj_bar, const T* s_out, const T* t_out,
+                             const T* u_hat, const T* wtu, T* w_bar, T* u_bar, T* b_bar, int64_t dim, int64_t batch) {
   FlowCfg c;
   const size_t nlg_max = nl < PP_NLG ? nl : PP_NLG;
   constexpr int VWr = Vec16<T>::N;
@@ -3414,7 +3409,41 @@ int planar_vjp_params_impl(bjx_ctx* ctx, const T* w, const T* u, const T* b, int
   }
   return BJX_OK;
 }
+
+template <class T>
+int planar_vjp_params_impl(bjx_ctx* ctx, const T* w, const T* u, const T* b, int nl, const T* in, const T* out_bar, const T* ladj_bar, T* in_bar,
+                           T* w_bar, T* u_bar, T* b_bar, T* work, int64_t dim, int64_t batch) {
+  BJX_REQUIRE(ctx, batch >= 1, BJX_ERR_SHAPE, "bjx_planar_vjp_params: empty batch");
+  T* s_out = work;                                   // [nl, batch]
+  T* t_out = work + (size_t)nl * batch;
+  int rc = planar_vjp_impl<T>(ctx, 0, w, u, b, nl, in, out_bar, ladj_bar, in_bar, dim, batch, t_out, s_out);
+  if (rc) return rc;
+  // tables left by planar_vjp_impl: û [nl][dim], wᵀû [nl] — in the scratch, or (a stack too large for it) at the head of the grown workspace
+  const T* u_hat = (((size_t)nl * dim + nl) * sizeof(T) + 255) / 256 * 256 > BJX_SCRATCH_BYTES ? static_cast<const T*>(ctx->big_ws) : static_cast<const T*>(ctx->scratch);
+  const T* wtu = u_hat + (size_t)nl * dim;
+  return planar_param_reduce_impl<T>(ctx, w, u, nl, in, out_bar, ladj_bar, s_out, t_out, u_hat, wtu, w_bar, u_bar, b_bar, dim, batch);
+}
 }  // namespace
+
+namespace bjx {
+template <class T>
+int planar_prep_launch(bjx_ctx* ctx, const T* w, const T* u, int nl, int64_t dim, T* u_hat, T* wtu) {
+  hipLaunchKernelGGL(planar_prep_kernel<T>, dim3(nl), dim3(256), 0, ctx->stream, w, u, dim, u_hat, wtu);
+  BJX_CHECK_LAUNCH(ctx);
+  return BJX_OK;
+}
+template <class T>
+int planar_param_reduce_launch(bjx_ctx* ctx, const T* w, const T* u, int nl, const T* in, const T* out_bar, const T* ladj_bar, const T* s_out, const T* t_out,
+                               const T* u_hat, const T* wtu, T* w_bar, T* u_bar, T* b_bar, int64_t dim, int64_t batch) {
+  return planar_param_reduce_impl<T>(ctx, w, u, nl, in, out_bar, ladj_bar, s_out, t_out, u_hat, wtu, w_bar, u_bar, b_bar, dim, batch);
+}
+template int planar_prep_launch<float>(bjx_ctx*, const float*, const float*, int, int64_t, float*, float*);
+template int planar_prep_launch<double>(bjx_ctx*, const double*, const double*, int, int64_t, double*, double*);
+template int planar_param_reduce_launch<float>(bjx_ctx*, const float*, const float*, int, const float*, const float*, const float*, const float*, const float*,
+                                               const float*, const float*, float*, float*, float*, int64_t, int64_t);
+template int planar_param_reduce_launch<double>(bjx_ctx*, const double*, const double*, int, const double*, const double*, const double*, const double*, const double*,
+                                                const double*, const double*, double*, double*, double*, int64_t, int64_t);
+}  // namespace bjx
 
 BJX_API int bjx_planar_vjp_params(bjx_ctx* ctx, bjx_dtype dt, const void* w, const void* u, const void* b, int n_layers, const void* in,
                                   const void* out_bar, const void* ladj_bar, void* in_bar, void* w_bar, void* u_bar, void* b_bar, void* work,

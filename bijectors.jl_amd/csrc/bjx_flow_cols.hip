@@ -16,29 +16,7 @@ using namespace bjx;
 // C dot products of a layer are reduced together (one butterfly each, one barrier per layer: the LDS slots alternate by layer parity).
 // Packs on element-aligned addresses, the last one partial.  C·R = 16 (8 at R = 1): 64 data registers.  (Blocks of 512 / 1 024 threads that keep
 // R small and C large beyond 4 096 rows: no faster at 512 — 153–179 registers — and spilled at 1 024.)
-__device__ __forceinline__ float lane_bcast(float v, int l) { return __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, v), l)); }
-__device__ __forceinline__ double lane_bcast(double v, int l) {
-  return __hiloint2double(__builtin_amdgcn_readlane(__double2hiint(v), l), __builtin_amdgcn_readlane(__double2loint(v), l));
-}
-template <int G> __device__ __forceinline__ float group_sum_fast(float v) { return group_sum_f32_dpp<G>(v); }
-template <int G> __device__ __forceinline__ double group_sum_fast(double v) { return group_sum<G>(v); }
-// C values per lane -> lane L holds the wave sum of value L / (64 / C): log2(C) halving exchanges (C/2 + C/4 + ... shuffles in all)
-// and one butterfly over the 64 / C lanes that are left, instead of C full butterflies (6·C shuffles).
-template <class T, int C, int G> __device__ __forceinline__ T wave_sum_scatter_rec(const T (&s)[C], int lane) {
-  if constexpr (C == 1) return group_sum_fast<G>(s[0]);
-  else {
-    constexpr int H = G / 2;
-    const bool hi = lane & H;
-    T a[C / 2];
-#pragma unroll
-    for (int i = 0; i < C / 2; ++i) a[i] = (hi ? s[C / 2 + i] : s[i]) + shfl_xor(hi ? s[i] : s[C / 2 + i], H);
-    return wave_sum_scatter_rec<T, C / 2, H>(a, lane);
-  }
-}
-template <class T, int C> __device__ __forceinline__ T wave_sum_scatter(const T (&s)[C], int lane) {
-  static_assert(C == 1 || C == 2 || C == 4 || C == 8 || C == 16, "C");
-  return wave_sum_scatter_rec<T, C, 64>(s, lane);
-}
+#include "bjx_flow_cols.inc"          // lane_bcast, wave_sum_scatter (shared with bjx_planar_logpdf.hip)
 
 template <class T, int V, int R, int C, bool INV, int NT>
 __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu((R <= 4 && sizeof(T) == 4) ? 4 : 1, 8))) void planar_vjp_cols_kernel(const PlanarArgs<T> A, const T* __restrict__ x, const T* __restrict__ ybar, const T* __restrict__ lbar,

@@ -224,6 +224,14 @@ int planar_vjp_cols_launch(bjx_ctx* ctx, int inverse, const T* w, const T* u_hat
 // the Float32 register-tile input pullback (bjx_flow_vjp_reg.hip); 1 = shape not served
 int planar_vjp_reg_launch(bjx_ctx* ctx, int inverse, const float* w, const float* u_hat, const float* wtu, const float* b, int nl, const float* in,
                           const float* out_bar, const float* ladj_bar, float* in_bar, int64_t dim, int64_t batch, float* t_out, float* s_out);
+// bjx_flow.hip, for bjx_planar_logpdf.hip: the û [nl][dim] / wᵀû [nl] tables of a stack (planar_prep_kernel, one launch), and the
+// reduction stage of bjx_planar_vjp_params — (w̄, ū, b̄) from Z₀ = `in`, the output cotangent, ℓ̄ (NULL = 0) and the (s̄, t) tables
+// [batch][nl] of a pullback sweep.  The stage is jointly linear in (out_bar, ladj_bar, s̄).
+template <class T>
+int planar_prep_launch(bjx_ctx* ctx, const T* w, const T* u, int nl, int64_t dim, T* u_hat, T* wtu);
+template <class T>
+int planar_param_reduce_launch(bjx_ctx* ctx, const T* w, const T* u, int nl, const T* in, const T* out_bar, const T* ladj_bar, const T* s_out, const T* t_out,
+                               const T* u_hat, const T* wtu, T* w_bar, T* u_bar, T* b_bar, int64_t dim, int64_t batch);
 }  // namespace bjx
 
 // ------------------------------------------------------------------ device math

@@ -1457,6 +1457,7 @@ class PlanarLayer(Bijector):
         self.b = torch.as_tensor(b).reshape(-1)
         self.n_layers = 1 if self.w.dim() == 1 else self.w.shape[1]
         self._tab = None
+        self._refused = set()                         # shapes bjx_planar_logpdf_vjp_params refused (logpdf_vjp_params)
 
     @classmethod
     def stack(cls, layers):
@@ -1517,6 +1518,7 @@ class _PlanarRun(PlanarLayer):
         self._tab = None
         self._srcs = None
         self._bufs = {}
+        self._refused = set()
 
     # (dim, n_layers) views of the parameters, for code that treats the run as one stacked layer (oracle comparisons, _key)
     @property
@@ -4049,15 +4051,21 @@ def _td_inverse(td):
 
 def _logpdf_grad_run(ib):
     """(run, single) when the plan of `ib` is one inverse(_RadialRun) — or one inverse(RadialLayer), a stack of one kept on the layer —,
-    else None."""
+    or one inverse(_PlanarRun) / inverse(PlanarLayer) (a PlanarLayer with a (dim, n_layers) matrix counts; the layer itself is the run),
+    else None.  single: the gradients are the layer's own dictionary, not {"stages": [...]}."""
     st = ib
-    if isinstance(ib, ComposedFunction):
-        plan = ib._plan()[0]
+    composed = isinstance(ib, ComposedFunction)
+    if composed:
+        plan, spans = ib._plan()
         if len(plan) != 1:
             return None
         st = plan[0]
     if not isinstance(st, Inverse):
         return None
+    if isinstance(st.orig, PlanarLayer):
+        if composed and (not isinstance(st.orig, _PlanarRun) or st.orig.n_layers != spans[0][1] - spans[0][0]):
+            return None                                 # a stage that is itself a stack: the generic path hands its tables back
+        return st.orig, not composed
     if isinstance(st.orig, _RadialRun):
         return st.orig, False
     if type(st.orig) is RadialLayer:
@@ -4106,6 +4114,48 @@ def _logpdf_grad_fused(run, single, d, yc, dim, batch, vec, lp_bar, params, want
     return lp, yb, {"transform": per[0] if single else {"stages": per[::-1]}, "base": base}       # stage j of inverse(run) is inverse(layer L-1-j)
 
 
+def _logpdf_grad_fused_planar(run, single, d, yc, dim, batch, vec, lp_bar, params, want_y_bar):
+    """One call of bjx_planar_logpdf_vjp_params (include/bjx_planar_logpdf.h); None when the entry refuses the shape."""
+    n = run.n_layers
+    w, u, b = run._tables(yc, dim)
+    mu = None if d.mu is None else _param(d.mu, yc).reshape(-1)
+    sigma = None if d.sigma is None else _param(d.sigma, yc).reshape(-1)
+    lb = _ladj_bar(lp_bar, batch, yc)
+    ctx = context(yc.device)
+    new = lambda k: torch.empty(k, dtype=yc.dtype, device=yc.device)
+    lp = new(batch)
+    yb = _empty(dim, batch, yc, vec) if want_y_bar else None
+    wb = ub = bb = mb = sb = work = None
+    if params:
+        wb, ub, bb = new(n * dim), new(n * dim), new(n)
+        mb = None if mu is None else new(dim)
+        sb = None if sigma is None else new(dim)
+        # bjx_planar_logpdf_work_elems: the (−s̄, t) tables, x, ȳ when it is not returned, ones when there is no cotangent (each part
+        # rounded up to 4 elements)
+        up4 = lambda k: (k + 3) // 4 * 4
+        work = new(max(up4(2 * n * batch) + up4(dim * batch) + (0 if want_y_bar else up4(dim * batch)) + (up4(batch) if lb is None else 0), 1))
+    rc = L.load().bjx_planar_logpdf_vjp_params(ctx.h, _dt(yc), _ptr(w), _ptr(u), _ptr(b), n, _ptr(mu), _ptr(sigma), _ptr(yc), _ptr(lb), _ptr(lp), _ptr(yb),
+                                               _ptr(wb), _ptr(ub), _ptr(bb), _ptr(mb), _ptr(sb), _ptr(work), dim, batch)
+    if rc == L.ERR_UNSUPPORTED:
+        return None
+    L.check(ctx.h, rc, "bjx_planar_logpdf_vjp_params")
+    if not params:
+        return lp, yb, {}
+    W, U = wb.reshape(n, dim).T, ub.reshape(n, dim).T                                  # (dim, n_layers), as vjp_params hands them back
+    if not single:                                                                       # stage j of inverse(run) is inverse(layer L-1-j)
+        G = {"stages": [{"w": W[:, k], "u": U[:, k], "b": bb[k:k + 1]} for k in range(n - 1, -1, -1)]}
+    elif n > 1 or isinstance(run, _PlanarRun) or run.w.dim() == 2:
+        G = {"w": W, "u": U, "b": bb}
+    else:
+        G = {"w": wb.reshape(w.shape), "u": ub.reshape(u.shape), "b": bb}
+    base = {}
+    if mb is not None:
+        base["mu"] = mb
+    if sb is not None:
+        base["sigma"] = sb
+    return lp, yb, {"transform": G, "base": base}
+
+
 def logpdf_vjp_params(td: TransformedDistribution, y, lp_bar=None, params=True, want_y_bar=True):
     """Value and gradients of `logpdf(td, y)` (the reference differentiates src/transformed_distribution.jl:164-169): the per-column
     log-density lp, the cotangent of y and — the step maximum-likelihood training of a flow takes — the cotangents of the
@@ -4120,8 +4170,10 @@ def logpdf_vjp_params(td: TransformedDistribution, y, lp_bar=None, params=True, 
 
     A flow that is a run of RadialLayers (or one RadialLayer) on a dense input takes ONE streaming pass over y
     (bjx_radial_stack_logpdf_vjp_params: the inverse sweep, the base density and the reverse sweep on the resident column) plus its
-    folds; shapes that entry refuses are remembered (per dtype, dim and whether μ̄ / σ̄ are asked for) and, like every other transform, go through `_preimage`, the arithmetic above
-    and `vjp_params` / `vjp` of the inverse."""
+    folds; a flow that is a run of PlanarLayers (or one PlanarLayer, a (dim, n_layers) stack included) takes one pass too
+    (bjx_planar_logpdf_vjp_params: one inverse sweep instead of three) plus the reduction stage of bjx_planar_vjp_params; shapes those
+    entries refuse are remembered (per dtype, dim and whether μ̄ / σ̄ are asked for) and, like every other transform, go through
+    `_preimage`, the arithmetic above and `vjp_params` / `vjp` of the inverse."""
     d = td.dist
     if not isinstance(d, MvNormal):
         raise NotImplementedError("logpdf_vjp_params: the base must be an MvNormal (standard or diagonal); other bases are not differentiated")
@@ -4140,8 +4192,9 @@ def logpdf_vjp_params(td: TransformedDistribution, y, lp_bar=None, params=True, 
         run, single = hit
         # what the entry refuses depends on whether the rows of μ̄ / σ̄ widen its tables: remembered per (dtype, dim, those rows asked for)
         key = ("logpdf", yc.dtype, dim, bool(params and (d.mu is not None or d.sigma is not None)))
-        if run._fused_ok(yc, dim) and key not in run._refused:
-            r = _logpdf_grad_fused(run, single, d, yc, dim, batch, vec, lp_bar, params, want_y_bar)
+        planar = isinstance(run, PlanarLayer)
+        if key not in run._refused and (planar or run._fused_ok(yc, dim)):
+            r = (_logpdf_grad_fused_planar if planar else _logpdf_grad_fused)(run, single, d, yc, dim, batch, vec, lp_bar, params, want_y_bar)
             if r is not None:
                 return r
             run._refused.add(key)
