@@ -1559,7 +1559,9 @@ __global__ __launch_bounds__(256) void bn_stats_reduce_kernel(const double* __re
 // cotangent z̄ of a chain `tail ∘ Shift(μ) ∘ Scale(σ)` and b = its input z these are the parameter cotangents of the
 // leading per-row affine stage — the mean-field family of ADVI:  μ̄ = Σ z̄/σ,  σ̄ = (Σ z̄ z + Σ ℓ̄)/σ.
 // Same streaming shape as bn_stats_kernel (lanes along the rows, Float64 accumulators, LDS combine, one partial per block).
-template <class T, int V, int R>
+// SHIFT (the batch statistics of columns taller than bn_stats_kernel's register accumulators): b is ONE value per row, the shift c of
+// bn_stats_kernel, and the sums are Σ (a - c), Σ (a - c)².
+template <class T, int V, int R, bool SHIFT = false>
 __global__ __launch_bounds__(256) void row_moments_kernel(const T* __restrict__ a, const T* __restrict__ b, int64_t dim, int64_t batch, int G,
                                                           double* __restrict__ partial, int64_t ld, int64_t prow) {
   // dim rows per WINDOW of columns that are ld elements apart; blockIdx.y picks the window (rows blockIdx.y * dim ... of the `prow`
@@ -1577,6 +1579,13 @@ __global__ __launch_bounds__(256) void row_moments_kernel(const T* __restrict__ 
   for (int k = 0; k < R; ++k)
 #pragma unroll
     for (int j = 0; j < V; ++j) { s1[k][j] = 0.0; s2[k][j] = 0.0; }
+  [[maybe_unused]] T sh[R][V];
+  if constexpr (SHIFT) {
+#pragma unroll
+    for (int k = 0; k < R; ++k)
+#pragma unroll
+      for (int j = 0; j < V; ++j) sh[k][j] = (b && gl + k * G < nvc) ? b[(int64_t)(gl + k * G) * V + j] : T(0);
+  }
   constexpr int U = R == 1 ? 4 : (R == 2 ? 2 : 1);
   const int64_t stride = (int64_t)gridDim.x * cols_per_block;
   for (int64_t col = (int64_t)blockIdx.x * cols_per_block + cg; col < batch; col += U * stride) {
@@ -1587,8 +1596,15 @@ __global__ __launch_bounds__(256) void row_moments_kernel(const T* __restrict__ 
       for (int k = 0; k < R; ++k) {
         const int64_t c = col + u * stride;
         const bool ok = c < batch && gl + k * G < nvc;
-        if (ok) { pa[u][k] = load_pack<T, V, false>(a + c * ld + (int64_t)(gl + k * G) * V); pb[u][k] = b ? load_pack<T, V, false>(b + c * ld + (int64_t)(gl + k * G) * V) : pa[u][k]; }
-        else {
+        if constexpr (SHIFT) {
+          if (ok) {
+            pa[u][k] = load_pack<T, V, false>(a + c * ld + (int64_t)(gl + k * G) * V);
+#pragma unroll
+            for (int j = 0; j < V; ++j) pa[u][k].v[j] -= sh[k][j];
+            pb[u][k] = pa[u][k];
+          }
+        } else if (ok) { pa[u][k] = load_pack<T, V, false>(a + c * ld + (int64_t)(gl + k * G) * V); pb[u][k] = b ? load_pack<T, V, false>(b + c * ld + (int64_t)(gl + k * G) * V) : pa[u][k]; }
+        if (!ok) {
 #pragma unroll
           for (int j = 0; j < V; ++j) { pa[u][k].v[j] = T(0); pb[u][k].v[j] = T(0); }
         }
@@ -1624,11 +1640,12 @@ __global__ __launch_bounds__(256) void row_moments_kernel(const T* __restrict__ 
 
 // Rows [r0, r0 + rows) in windows of `win` rows (a multiple of V; one pack per lane: four columns in flight), the windows as
 // blockIdx.y of ONE launch, then one fixed-order reduction of the block partials over all of them.
-template <class T, int V>
+template <class T, int V, bool SHIFT = false>
 int row_moments_windows(bjx_ctx* ctx, const T* a, const T* b, double* out, int64_t dim, int64_t batch, int64_t r0, int64_t rows, int64_t win) {
+  const char* who = SHIFT ? "bjx_batchnorm_stats" : "bjx_row_moments";
   if (win > rows) win = rows;
   const int64_t nwin = (rows + win - 1) / win;
-  BJX_REQUIRE(ctx, nwin < 65536, BJX_ERR_UNSUPPORTED, "bjx_row_moments: too many rows");
+  BJX_REQUIRE(ctx, nwin < 65536, BJX_ERR_UNSUPPORTED, "%s: too many rows", who);
   const int64_t nvc = win / V;
   int G = 1;
   while (G < 64 && G < nvc) G <<= 1;
@@ -1639,11 +1656,11 @@ int row_moments_windows(bjx_ctx* ctx, const T* a, const T* b, double* out, int64
   if (nblocks < 1) nblocks = 1;
   { int rc = bjx_ensure_partials(ctx, (size_t)nblocks * rows * 2); if (rc) return rc; }
   const size_t smem = (size_t)cols_per_block * win * 2 * sizeof(double);
-  BJX_REQUIRE(ctx, smem <= BJX_LDS_MAX, BJX_ERR_UNSUPPORTED, "bjx_row_moments: LDS");
+  BJX_REQUIRE(ctx, smem <= BJX_LDS_MAX, BJX_ERR_UNSUPPORTED, "%s: LDS", who);
   {
     BjxProf prof_(ctx);
-    bjx_allow_big_lds(row_moments_kernel<T, V, 1>, smem);
-    hipLaunchKernelGGL((row_moments_kernel<T, V, 1>), dim3(nblocks, (unsigned)nwin), dim3(256), smem, ctx->stream, a + r0, b ? b + r0 : nullptr, win, batch, G, ctx->partials, dim, rows);
+    bjx_allow_big_lds(row_moments_kernel<T, V, 1, SHIFT>, smem);
+    hipLaunchKernelGGL((row_moments_kernel<T, V, 1, SHIFT>), dim3(nblocks, (unsigned)nwin), dim3(256), smem, ctx->stream, a + r0, b ? b + r0 : nullptr, win, batch, G, ctx->partials, dim, rows);
   }
   BJX_CHECK_LAUNCH(ctx);
   { BjxProf prof_(ctx);
@@ -1818,7 +1835,18 @@ template <class T>
 int bn_stats_impl(bjx_ctx* ctx, const T* shift, const T* in, double* stats, double* partial, int max_blocks, int64_t dim, int64_t batch) {
   ColLaunch c = col_launch_cfg<T>(ctx, in, in, dim, batch);
   const int64_t nvc = dim / c.V;
-  BJX_REQUIRE(ctx, nvc <= 256, BJX_ERR_UNSUPPORTED, "bjx_batchnorm_train: %lld channels exceed the register-accumulator kernel (max %d)", (long long)dim, 256 * c.V);
+  if (nvc > 256) {
+    // Columns of more than 256 packs (the register accumulators of bn_stats_kernel; one-element packs when dim is no multiple of the
+    // pack width or `in` is not 16-byte aligned: 257 rows were REFUSED, and every height above 1024 / 512): the windows of
+    // bjx_row_moments with the per-row shift — whole 16-byte packs on element-aligned addresses in windows of 64 packs (blockIdx.y), the
+    // dim mod VW rows that are left as one-element packs, each with its fixed-order reduce: 2 launches, 4 when dim mod VW != 0,
+    // whatever the batch.  The block partials live in the context's partial buffer, not in the scratch.
+    constexpr int VWw = Vec16<T>::N;
+    const int64_t whole = dim / VWw * VWw;
+    { const int rc = row_moments_windows<T, VWw, true>(ctx, in, shift, stats, dim, batch, 0, whole, (int64_t)64 * VWw); if (rc) return rc; }
+    if (whole < dim) { const int rc = row_moments_windows<T, 1, true>(ctx, in, shift, stats, dim, batch, whole, dim - whole, 64); if (rc) return rc; }
+    return BJX_OK;
+  }
   const int R = nvc <= c.G ? 1 : (nvc <= 2 * c.G ? 2 : 4);
   const int cols_per_block = 256 / c.G;
   int nblocks = (int)((batch + cols_per_block * 16 - 1) / (cols_per_block * 16));     // >= 16 columns per lane group
@@ -1846,6 +1874,8 @@ int bn_stats_impl(bjx_ctx* ctx, const T* shift, const T* in, double* stats, doub
 // scratch layout of the training path: [stats 2 dim + 1 (+1 pad)][partials max_blocks*dim*2] doubles, then batch m / v (T)
 template <class T> struct BnScratch {
   double* stats; double* partial; T* m_batch; T* v_batch; int max_blocks; bool ok;
+  // the tallest column with room for one set of partials: 26 214 channels in Float32, 21 845 in Float64 (include/bjx.h)
+  static constexpr long long max_dim = (long long)((BJX_SCRATCH_BYTES - 2 * sizeof(double)) / (4 * sizeof(double) + 2 * sizeof(T)));
   BnScratch(bjx_ctx* ctx, int64_t dim) {
     const size_t stats_n = 2 * (size_t)dim + 1;
     const size_t fixed = (stats_n + 1) * sizeof(double) + 2 * (size_t)dim * sizeof(T);
@@ -1864,7 +1894,7 @@ template <class T>
 int bn_apply_stats_impl(bjx_ctx* ctx, const T* b, const T* logs, T* m, T* v, T eps, T mtm, const double* stats, const T* in, T* out, T* ladj_ps,
                         double* ladj_sum, int64_t dim, int64_t batch, uint32_t flags) {
   BnScratch<T> sc(ctx, dim);
-  BJX_REQUIRE(ctx, sc.ok, BJX_ERR_UNSUPPORTED, "bjx_batchnorm_train: scratch too small for %lld channels", (long long)dim);
+  BJX_REQUIRE(ctx, sc.ok, BJX_ERR_UNSUPPORTED, "bjx_batchnorm_train: %lld channels exceed the context scratch (max %lld)", (long long)dim, BnScratch<T>::max_dim);
   hipLaunchKernelGGL(bn_train_finalize_kernel<T>, dim3(1), dim3(256), 0, ctx->stream, stats, dim, logs, eps, mtm, m, v, sc.m_batch, sc.v_batch, batch, ctx->consts);
   BJX_CHECK_LAUNCH(ctx);
   const bool lds = (size_t)dim * 4 * sizeof(T) <= 60 * 1024;
@@ -1878,7 +1908,7 @@ int bn_train_impl(bjx_ctx* ctx, const T* b, const T* logs, T* m, T* v, T eps, T 
                   int64_t dim, int64_t batch, uint32_t flags) {
   BJX_REQUIRE(ctx, batch >= 1, BJX_ERR_SHAPE, "bjx_batchnorm_train: empty batch");
   BnScratch<T> sc(ctx, dim);
-  BJX_REQUIRE(ctx, sc.ok, BJX_ERR_UNSUPPORTED, "bjx_batchnorm_train: scratch too small for %lld channels", (long long)dim);
+  BJX_REQUIRE(ctx, sc.ok, BJX_ERR_UNSUPPORTED, "bjx_batchnorm_train: %lld channels exceed the context scratch (max %lld)", (long long)dim, BnScratch<T>::max_dim);
   int rc = bn_stats_impl<T>(ctx, m, in, sc.stats, sc.partial, sc.max_blocks, dim, batch);
   if (rc) return rc;
   if (ctx->comm && ctx->nranks > 1) {      // batch sharded over GPUs: the second collective of SURVEY.md §8(e)
@@ -1894,9 +1924,9 @@ BJX_API int bjx_batchnorm_stats(bjx_ctx* ctx, bjx_dtype dt, const void* shift, c
   BJX_REQUIRE(ctx, dim >= 1 && batch >= 0, BJX_ERR_SHAPE, "bjx_batchnorm_stats: bad size");
   BJX_REQUIRE(ctx, stats && (in || batch == 0), BJX_ERR_ARG, "bjx_batchnorm_stats: null pointer");
   if (batch == 0) { BJX_HIP(ctx, hipMemsetAsync(stats, 0, (size_t)(2 * dim + 1) * sizeof(double), ctx->stream)); return BJX_OK; }
-  if (dt == BJX_F32) { BnScratch<float> sc(ctx, dim); BJX_REQUIRE(ctx, sc.ok, BJX_ERR_UNSUPPORTED, "bjx_batchnorm_stats: too many channels");
+  if (dt == BJX_F32) { BnScratch<float> sc(ctx, dim); BJX_REQUIRE(ctx, sc.ok, BJX_ERR_UNSUPPORTED, "bjx_batchnorm_stats: %lld channels exceed the context scratch (max %lld)", (long long)dim, BnScratch<float>::max_dim);
     return bn_stats_impl<float>(ctx, (const float*)shift, (const float*)in, stats, sc.partial, sc.max_blocks, dim, batch); }
-  if (dt == BJX_F64) { BnScratch<double> sc(ctx, dim); BJX_REQUIRE(ctx, sc.ok, BJX_ERR_UNSUPPORTED, "bjx_batchnorm_stats: too many channels");
+  if (dt == BJX_F64) { BnScratch<double> sc(ctx, dim); BJX_REQUIRE(ctx, sc.ok, BJX_ERR_UNSUPPORTED, "bjx_batchnorm_stats: %lld channels exceed the context scratch (max %lld)", (long long)dim, BnScratch<double>::max_dim);
     return bn_stats_impl<double>(ctx, (const double*)shift, (const double*)in, stats, sc.partial, sc.max_blocks, dim, batch); }
   return bjx_fail(ctx, BJX_ERR_ARG, "bjx_batchnorm_stats: bad dtype %d", (int)dt);
 }
@@ -1964,7 +1994,8 @@ __global__ __launch_bounds__(256) void bn_train_vjp_apply_kernel(const T* __rest
 template <class T>
 int bn_train_vjp_impl(bjx_ctx* ctx, const T* logs, const T* mean, const T* var, double eps, const double* mom, const double* lsum, const T* in,
                       const T* out_bar, T* in_bar, T* b_bar, T* logs_bar, int64_t dim, int64_t batch) {
-  BJX_REQUIRE(ctx, (size_t)3 * dim * sizeof(T) <= BJX_SCRATCH_BYTES, BJX_ERR_UNSUPPORTED, "bjx_batchnorm_train_vjp: too many channels");
+  BJX_REQUIRE(ctx, (size_t)3 * dim * sizeof(T) <= BJX_SCRATCH_BYTES, BJX_ERR_UNSUPPORTED, "bjx_batchnorm_train_vjp: %lld channels exceed the coefficient table in the context scratch (max %lld)",
+              (long long)dim, (long long)(BJX_SCRATCH_BYTES / (3 * sizeof(T))));
   T* coef = reinterpret_cast<T*>(ctx->scratch);
   hipLaunchKernelGGL((bn_train_vjp_coef_kernel<T>), dim3((unsigned)((dim + 255) / 256)), dim3(256), 0, ctx->stream, logs, mean, var, eps, mom, lsum, (int)dim, coef, b_bar, logs_bar);
   BJX_CHECK_LAUNCH(ctx);

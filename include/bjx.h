@@ -353,7 +353,8 @@ int bjx_batchnorm(bjx_ctx* ctx, bjx_dtype dt, int inverse, const void* b, const 
                   void* ladj_ps, double* ladj_sum, int64_t dim, int64_t batch, uint32_t flags);
 
 /* Row moments over the batch: out[i] = sum_n a[i,n], out[dim+i] = sum_n a[i,n]*b[i,n] (b NULL: a^2), out[2 dim] = batch;
- * out: device double[2*dim+1], Float64 accumulation in a fixed order.  With a = the input cotangent of a chain
+ * out: device double[2*dim+1], Float64 accumulation in a fixed order; any number of rows, `a` / `b` need no alignment beyond their
+ * element type; batch == 0 writes zeros.  With a = the input cotangent of a chain
  * `tail o Shift(mu) o Scale(sigma)` (bjx_stacked_vjp) and b = its input these are the parameter cotangents of the
  * leading per-row affine stage (mean-field families): mu_bar = out[i]/sigma, sigma_bar = (out[dim+i] + sum ladj_bar)/sigma.
  * A batch sharded over GPUs all-reduces `out` (bjx_allreduce_sum_f64). */
@@ -365,7 +366,12 @@ int bjx_row_moments(bjx_ctx* ctx, bjx_dtype dt, const void* a, const void* b, do
  * (bn.v with the n/(n-1) correction, :59).  When the context has a communicator (bjx_comm_init) the batch is
  * taken to be sharded over the ranks and the 2·dim+1 Float64 sums (Σx, Σx², n) are all-reduced once
  * (SURVEY.md §8e): every rank then normalises with the GLOBAL statistics.  The reference has no inverse in
- * training mode (:71). */
+ * training mode (:71).
+ * Limits: batch >= 1 (BJX_ERR_SHAPE otherwise);
+ * dim <= 26 214 (Float32) / 21 845 (Float64) — the statistics, one set of block partials and the batch mean / variance share the
+ * 1 MiB context scratch: (6 dim + 2) doubles + 2 dim T; beyond it BJX_ERR_UNSUPPORTED before any launch, nothing written, `m` and
+ * `v` untouched.  in / out need no alignment beyond their element type (whole aligned 16-byte packs are the fast form).
+ * ladj_ps (device T[batch]) and ladj_sum (device double[1]) may each be NULL; BJX_ACCUMULATE adds to both. */
 int bjx_batchnorm_train(bjx_ctx* ctx, bjx_dtype dt, const void* b, const void* logs, void* m, void* v,
                         double eps, double mtm, const void* in, void* out, void* ladj_ps,
                         double* ladj_sum, int64_t dim, int64_t batch, uint32_t flags);
@@ -375,10 +381,16 @@ int bjx_batchnorm_train(bjx_ctx* ctx, bjx_dtype dt, const void* b, const void* l
  *                              stats[2 dim] = batch  — device double[2 dim + 1], Float64, fixed summation order.
  *                              `shift` (device T[dim] or NULL = 0) must be identical on every rank: pass the moving
  *                              mean `m`, which makes the one-pass variance as well conditioned as normalise.jl:54's two-pass form.
+ *                              batch == 0 writes zeros (`in` may be NULL then).  2 kernel launches whatever the batch; 4 when the
+ *                              columns have more than 256 packs (dim > 1024 Float32 / 512 Float64; dim > 256 when dim is no
+ *                              multiple of the 16-byte pack or `in` is not 16-byte aligned) AND dim is no multiple of the pack.
+ *                              A NaN in row i makes stats[i] and stats[dim+i] NaN and nothing else.
  *   (host)                     sum `stats` over the ranks (bjx_allreduce_sum_f64 / MPI / torch.distributed)
  *   bjx_batchnorm_train_apply  statistics from the GLOBAL sums (shift = the `m` passed in, read before it is updated),
  *                              moving-statistics update (:58-59), transform and log-det of THIS rank's columns.
- * bjx_batchnorm_train(x) == stats(m, x) -> all-reduce when the context has a communicator -> train_apply. */
+ * bjx_batchnorm_train(x) == stats(m, x) -> all-reduce when the context has a communicator -> train_apply, bit for bit.
+ * Both halves have the limits of bjx_batchnorm_train (dim <= 26 214 / 21 845: BJX_ERR_UNSUPPORTED before any launch, nothing
+ * written); train_apply takes the NULLs and flags of bjx_batchnorm_train. */
 int bjx_batchnorm_stats(bjx_ctx* ctx, bjx_dtype dt, const void* shift, const void* in, double* stats, int64_t dim, int64_t batch);
 int bjx_batchnorm_train_apply(bjx_ctx* ctx, bjx_dtype dt, const void* b, const void* logs, void* m, void* v,
                               double eps, double mtm, const double* stats, const void* in, void* out, void* ladj_ps,
@@ -392,8 +404,11 @@ int bjx_batchnorm_train_apply(bjx_ctx* ctx, bjx_dtype dt, const void* b, const v
  * mean, var: device T[dim], the batch statistics the forward pass normalised with (from the sums of bjx_batchnorm_stats).
  * moments: device double[2 dim + 1] = (sum_n out_bar, sum_n out_bar*in, N) of the WHOLE batch: bjx_row_moments(out_bar, in) on
  * this rank's columns, summed over the ranks by the host — the one extra all-reduce of a sharded training step.
- * ladj_bar_sum: device double[1] = sum_n ladj_bar over the whole batch, or NULL (= 0).  in_bar (may not alias in), b_bar,
- * logs_bar (device T[dim]) may each be NULL. */
+ * ladj_bar_sum: device double[1] = sum_n ladj_bar over the whole batch, or NULL (= 0).  in_bar, b_bar, logs_bar (device T[dim]) may
+ * each be NULL: with in_bar == NULL only the parameter cotangents are written (`in` and out_bar are not read).  in_bar may alias
+ * out_bar (same bits as separate buffers) but not `in` (BJX_ERR_ARG, nothing written).  No operand needs more than its element
+ * type's alignment.  dim <= 87 381 (Float32) / 43 690 (Float64): 3 dim T of per-channel coefficients in the 1 MiB context scratch;
+ * beyond it BJX_ERR_UNSUPPORTED before any launch, nothing written. */
 int bjx_batchnorm_train_vjp(bjx_ctx* ctx, bjx_dtype dt, const void* logs, const void* mean, const void* var, double eps,
                             const double* moments, const double* ladj_bar_sum, const void* in, const void* out_bar,
                             void* in_bar, void* b_bar, void* logs_bar, int64_t dim, int64_t batch);
