@@ -19,6 +19,8 @@
 //   chain_colgroup_kernel : G lanes per column, additionally writes the per-sample log-det vector.
 #include "bjx_internal.h"
 
+#include <type_traits>
+
 namespace {
 using namespace bjx;
 
@@ -28,10 +30,24 @@ template <class T> struct DevOp {
   const T* v0;         // device params (scalar if plen==1) or null
   const T* v1;
 };
+// ROWMODE 0 (no stage has per-row parameters): the chain as a resolved program, by value in the kernarg segment.
+// Everything the stage loop needs is known on the host at launch except the value of a device-resident scalar.
+// The scalars travel as their BITS (ParamBits): the stage loop carries them from stage to stage, and the compiler gives a loop-carried
+// uniform integer a scalar register but a loop-carried uniform float a vector register (16 more VGPRs: one wave less per SIMD).
+template <class T> using ParamBits = typename std::conditional<sizeof(T) == 4, uint32_t, uint64_t>::type;
+template <class T> struct ScalarProg {
+  uint32_t kinds;               // 4 bits per stage (BJX_OP_* <= 13), stage 0 in the lowest
+  uint32_t dev;                 // bit 2k: the first scalar of stage k is *va[k]; bit 2k + 1: the second is *vb[k]
+  ParamBits<T> a[BJX_MAX_OPS], b[BJX_MAX_OPS];
+  const T* va[BJX_MAX_OPS];     // dev != 0: EVERY entry is readable (unused ones point at the context's constants)
+  const T* vb[BJX_MAX_OPS];
+};
 template <class T> struct ChainArgs {
   DevOp<T> ops[BJX_MAX_OPS];
   int n_ops;
+  ScalarProg<T> sp;             // filled when no stage has per-row parameters
 };
+static_assert(BJX_OP_STDNORMAL_LOGPDF < 16 && BJX_MAX_OPS * 4 <= 32, "ScalarProg packs a kind into 4 bits");
 
 // ROWMODE: 0 no per-row parameters; 1 the V rows of a pack are contiguous and 16-byte aligned
 //          (dim % V == 0): one vector load per parameter (L1/L2-resident table, <= a few KiB);
@@ -269,17 +285,8 @@ __device__ __forceinline__ bool kind_has_params(int kind) {
 // as the data pack itself, and two vector-parameter stages tripled the load traffic of a density chain.
 template <class T, int V, int U, int ROWMODE, bool SAMEROW = false, bool LSUM = false>
 __device__ __forceinline__ void apply_op(const DevOp<T>& op, Pack<T, V> (&p)[U], const int64_t (&r)[U], int64_t dim, T (&l)[U]) {
+  static_assert(ROWMODE != 0, "scalar-only chains run as a resolved program (run_prog)");
   const int kind = op.kind;
-  if constexpr (ROWMODE == 0 && sizeof(T) == 8) {
-    // scalar parameters, Float64: ONE parameter pack for the U packs (UA = 1) — lets the Logit stage take its two-log form
-    // (the Float32 instantiations keep the round-2 code path: the C2 headline kernel is not touched)
-    T a1[1][V], b1[1][V];
-#pragma unroll
-    for (int j = 0; j < V; ++j) { a1[0][j] = T(0); b1[0][j] = T(0); }
-    if (kind_has_params(kind)) load_params<T, V, ROWMODE>(op, r[0], dim, a1[0], b1[0]);
-    apply_kind<T, V, U, 1, LSUM>(kind, p, a1, b1, l);
-    return;
-  }
   T a[U][V], b[U][V];
   if (kind_has_params(kind)) {
     if constexpr (SAMEROW && U > 1) {
@@ -328,10 +335,73 @@ __device__ __forceinline__ void apply_chain_u_prefetch(const ChainArgs<T>& A, Pa
     for (int j = 0; j < V; ++j) { a[0][j] = an[0][j]; b[0][j] = bn[0][j]; }
   }
 }
+// ROWMODE 0: the whole program in scalar registers.  load_prog is the kernel's FIRST statement: the kinds and the host scalars are
+// scalar loads from the kernarg segment, a device-resident scalar is one uniform load through its pointer, all of them issued
+// together and ahead of the data packs, so their one wait falls inside the data's.  The stage loop below then touches no memory:
+// it shifts the next kind out of a register and steps two queues of scalar registers down.  (The descriptor loop this replaces went back to
+// memory per stage — kind, then plen and the pointers, then the scalars through a select of ADDRESSES, kernarg slot or device
+// pointer, i.e. two vector loads of values that sat in the kernarg segment — with every wait after the data had landed.)
+template <class T> struct ProgRegs {
+  uint32_t kinds;
+  int n_ops;
+  ParamBits<T> a[BJX_MAX_OPS], b[BJX_MAX_OPS];
+};
+template <class T, int ROWMODE>
+__device__ __forceinline__ ProgRegs<T> load_prog(const ChainArgs<T>& A) {
+  ProgRegs<T> P;
+  P.kinds = 0;
+  P.n_ops = 0;
+#pragma unroll
+  for (int k = 0; k < BJX_MAX_OPS; ++k) { P.a[k] = 0; P.b[k] = 0; }
+  if constexpr (ROWMODE == 0) {
+    P.kinds = A.sp.kinds;
+    P.n_ops = A.n_ops;
+#pragma unroll
+    for (int k = 0; k < BJX_MAX_OPS; ++k) { P.a[k] = A.sp.a[k]; P.b[k] = A.sp.b[k]; }
+    const uint32_t dev = A.sp.dev;
+    if (dev) {                                        // uniform; the VALUE is selected, never the address
+      ParamBits<T> da[BJX_MAX_OPS], db[BJX_MAX_OPS];
+#pragma unroll
+      for (int k = 0; k < BJX_MAX_OPS; ++k) {
+        da[k] = *reinterpret_cast<const ParamBits<T>*>(A.sp.va[k]);
+        db[k] = *reinterpret_cast<const ParamBits<T>*>(A.sp.vb[k]);
+      }
+#pragma unroll
+      for (int k = 0; k < BJX_MAX_OPS; ++k) {
+        P.a[k] = (dev >> (2 * k)) & 1u ? da[k] : P.a[k];
+        P.b[k] = (dev >> (2 * k + 1)) & 1u ? db[k] : P.b[k];
+      }
+    }
+  }
+  return P;
+}
+template <class T, int V, int U, bool LSUM>
+__device__ __forceinline__ void run_prog(const ProgRegs<T>& P, Pack<T, V> (&p)[U], T (&lu)[U]) {
+#pragma unroll
+  for (int u = 0; u < U; ++u) lu[u] = T(0);
+  // Rolled: a stage's arithmetic stays one piece of code, so nothing contracts across stages.  The kinds and the values are QUEUES
+  // that move down one place per stage (scalar moves of the values' bits; indexing the registers by k is a chain of selects per stage).
+  uint32_t kinds = P.kinds;
+  ParamBits<T> qa[BJX_MAX_OPS], qb[BJX_MAX_OPS];
+#pragma unroll
+  for (int k = 0; k < BJX_MAX_OPS; ++k) { qa[k] = P.a[k]; qb[k] = P.b[k]; }
+  for (int k = 0; k < P.n_ops; ++k) {
+    T a1[1][V], b1[1][V];
+    const T sa = __builtin_bit_cast(T, qa[0]), sb = __builtin_bit_cast(T, qb[0]);
+#pragma unroll
+    for (int j = 0; j < V; ++j) { a1[0][j] = sa; b1[0][j] = sb; }
+    const int kind = (int)(kinds & 15u);
+    kinds >>= 4;
+#pragma unroll
+    for (int i = 0; i + 1 < BJX_MAX_OPS; ++i) { qa[i] = qa[i + 1]; qb[i] = qb[i + 1]; }
+    apply_kind<T, V, U, 1, LSUM>(kind, p, a1, b1, lu);      // one parameter pack for the U packs (Float64: Logit's two-log form)
+  }
+}
 template <class T, int V, int U, int ROWMODE, bool SAMEROW = false, bool LSUM = false>
-__device__ __forceinline__ void apply_chain_u(const ChainArgs<T>& A, Pack<T, V> (&p)[U], const int64_t (&r)[U], int64_t dim, T (&lu)[U]) {
-  // scalar-only chains keep the plain loop: nothing but one s_load to cover, and the look-ahead's copies cost 2-6 % (same-call A/B)
-  if constexpr (ROWMODE != 0 && (SAMEROW || U == 1)) {
+__device__ __forceinline__ void apply_chain_u(const ChainArgs<T>& A, const ProgRegs<T>& P, Pack<T, V> (&p)[U], const int64_t (&r)[U], int64_t dim, T (&lu)[U]) {
+  if constexpr (ROWMODE == 0) {
+    run_prog<T, V, U, LSUM>(P, p, lu);
+  } else if constexpr (SAMEROW || U == 1) {
     apply_chain_u_prefetch<T, V, U, ROWMODE, LSUM>(A, p, r[0], dim, lu);
   } else {
 #pragma unroll
@@ -340,9 +410,9 @@ __device__ __forceinline__ void apply_chain_u(const ChainArgs<T>& A, Pack<T, V> 
   }
 }
 template <class T, int V, int U, int ROWMODE, bool SAMEROW = false>
-__device__ __forceinline__ T apply_chain(const ChainArgs<T>& A, Pack<T, V> (&p)[U], const int64_t (&r)[U], int64_t dim) {
+__device__ __forceinline__ T apply_chain(const ChainArgs<T>& A, const ProgRegs<T>& P, Pack<T, V> (&p)[U], const int64_t (&r)[U], int64_t dim) {
   T lu[U];
-  apply_chain_u<T, V, U, ROWMODE, SAMEROW, true>(A, p, r, dim, lu);
+  apply_chain_u<T, V, U, ROWMODE, SAMEROW, true>(A, P, p, r, dim, lu);
   T l = lu[0];
 #pragma unroll
   for (int u = 1; u < U; ++u) l += lu[u];
@@ -369,6 +439,7 @@ template <class T, int V, int ROWMODE, bool NT, int U, bool GEN = false>
 __global__ __launch_bounds__(256) void chain_flat_kernel(const ChainArgs<T> A, const T* x, T* y, int64_t n,
                                                          int64_t dim, int dim_pow2, const BjxFin fin, uint64_t seed = 0, int64_t e0 = 0) {
   __shared__ double red[4];
+  const ProgRegs<T> P = load_prog<T, ROWMODE>(A);
   const int64_t nv = n / V;
   const int64_t i0 = (int64_t)blockIdx.x * (256 * U) + threadIdx.x;
   double acc = 0.0;
@@ -392,8 +463,8 @@ __global__ __launch_bounds__(256) void chain_flat_kernel(const ChainArgs<T> A, c
       }
     }
     T l;
-    if (ROWMODE == 1 && U > 1 && (256 * V) % dim == 0) l = apply_chain<T, V, U, ROWMODE, true>(A, p, r, dim);   // same rows in every pack
-    else l = apply_chain<T, V, U, ROWMODE>(A, p, r, dim);
+    if (ROWMODE == 1 && U > 1 && (256 * V) % dim == 0) l = apply_chain<T, V, U, ROWMODE, true>(A, P, p, r, dim);   // same rows in every pack
+    else l = apply_chain<T, V, U, ROWMODE>(A, P, p, r, dim);
     if (y) {
 #pragma unroll
       for (int u = 0; u < U; ++u) store_pack<T, V, NT>(y + (i0 + u * 256) * V, p[u]);
@@ -409,7 +480,7 @@ __global__ __launch_bounds__(256) void chain_flat_kernel(const ChainArgs<T> A, c
         p[0] = GEN ? gen_pack<T, V>(seed, e0 + i * V) : load_pack<T, V, NT>(x + i * V);
         int64_t r[1] = {0};
         if constexpr (ROWMODE != 0) r[0] = (i * V) % dim;
-        T l = apply_chain<T, V, 1, ROWMODE>(A, p, r, dim);
+        T l = apply_chain<T, V, 1, ROWMODE>(A, P, p, r, dim);
         if (y) store_pack<T, V, NT>(y + i * V, p[0]);
         acc += (double)l;
       } else if (V > 1 && i == nv) {
@@ -417,7 +488,7 @@ __global__ __launch_bounds__(256) void chain_flat_kernel(const ChainArgs<T> A, c
           Pack<T, 1> q[1];
           q[0].v[0] = GEN ? gen_pack<T, 1>(seed, e0 + e).v[0] : x[e];
           int64_t r[1] = {ROWMODE == 0 ? 0 : e % dim};
-          T l = apply_chain<T, 1, 1, (ROWMODE == 0 ? 0 : 2)>(A, q, r, dim);
+          T l = apply_chain<T, 1, 1, (ROWMODE == 0 ? 0 : 2)>(A, P, q, r, dim);
           if (y) y[e] = q[0].v[0];
           acc += (double)l;
         }
@@ -436,6 +507,7 @@ template <class T, int V, int ROWMODE, bool NT, int U, int G>
 __global__ __launch_bounds__(256) void chain_flatcol_kernel(const ChainArgs<T> A, const T* x, T* y, T* ladj_ps, int64_t n, int64_t dim,
                                                             double c_ps_host, const double* c_ps_dev, int accumulate, double* partials) {
   __shared__ double red[4];
+  const ProgRegs<T> P = load_prog<T, ROWMODE>(A);
   const int64_t nv = n / V;                         // dim % V == 0 here: no element tail
   const int64_t i0 = (int64_t)blockIdx.x * (256 * U) + threadIdx.x;
   const int gl = threadIdx.x & (G - 1);
@@ -454,7 +526,7 @@ __global__ __launch_bounds__(256) void chain_flatcol_kernel(const ChainArgs<T> A
     r[u] = (int64_t)gl * V;                         // row of the pack inside its column
   }
   T lu[U];
-  apply_chain_u<T, V, U, ROWMODE, true>(A, p, r, dim, lu);      // r[u] = gl·V for every pack
+  apply_chain_u<T, V, U, ROWMODE, true>(A, P, p, r, dim, lu);      // r[u] = gl·V for every pack
   const double c_ps = c_ps_host + (c_ps_dev ? *c_ps_dev : 0.0);
 #pragma unroll
   for (int u = 0; u < U; ++u) {
@@ -485,6 +557,7 @@ __global__ __launch_bounds__(256) void chain_colgroup_kernel(const ChainArgs<T> 
                                                              const double* c_ps_dev, int accumulate,
                                                              double* partials) {
   __shared__ double red[4];
+  const ProgRegs<T> P = load_prog<T, ROWMODE>(A);
   const int gl = threadIdx.x & (G - 1);            // lane within the column group
   const int cols_per_block = 256 / G;
   const int64_t col = (int64_t)blockIdx.x * cols_per_block + threadIdx.x / G;
@@ -501,7 +574,7 @@ __global__ __launch_bounds__(256) void chain_colgroup_kernel(const ChainArgs<T> 
         int64_t r[CHAIN_U];
 #pragma unroll
         for (int u = 0; u < CHAIN_U; ++u) { p[u] = load_pack<T, V, NT>(xc + (v + (int64_t)u * G) * V); r[u] = (v + (int64_t)u * G) * V; }
-        l += apply_chain<T, V, CHAIN_U, ROWMODE>(A, p, r, dim);
+        l += apply_chain<T, V, CHAIN_U, ROWMODE>(A, P, p, r, dim);
 #pragma unroll
         for (int u = 0; u < CHAIN_U; ++u) if (y) store_pack<T, V, NT>(yc + (v + (int64_t)u * G) * V, p[u]);
       }
@@ -525,7 +598,7 @@ __global__ __launch_bounds__(256) void chain_colgroup_kernel(const ChainArgs<T> 
         }
       }
       T lu[UR];
-      apply_chain_u<T, V, UR, ROWMODE, false>(A, p, r, dim, lu);
+      apply_chain_u<T, V, UR, ROWMODE, false>(A, P, p, r, dim, lu);
 #pragma unroll
       for (int u = 0; u < UR; ++u) {
         if (ok[u]) {
@@ -543,7 +616,7 @@ __global__ __launch_bounds__(256) void chain_colgroup_kernel(const ChainArgs<T> 
           Pack<T, 1> p1[1];
           int64_t r1[1] = {nvc * V + t};
           p1[0].v[0] = xc[r1[0]];
-          l += apply_chain<T, 1, 1, (ROWMODE == 0 ? 0 : 2)>(A, p1, r1, dim);
+          l += apply_chain<T, 1, 1, (ROWMODE == 0 ? 0 : 2)>(A, P, p1, r1, dim);
           if (y) yc[r1[0]] = p1[0].v[0];
         }
       }
@@ -570,6 +643,7 @@ template <class T, int DIM, int ROWMODE, bool NT, int UC>
 __global__ __launch_bounds__(256) void chain_tiny_kernel(const ChainArgs<T> A, const T* __restrict__ x, T* __restrict__ y, T* __restrict__ ladj_ps, int64_t batch,
                                                          double c_ps_host, const double* c_ps_dev, int accumulate, double* partials) {
   __shared__ double red[4];
+  const ProgRegs<T> P = load_prog<T, ROWMODE>(A);
   const int64_t col0 = (int64_t)blockIdx.x * (256 * UC) + threadIdx.x;
   Pack<T, 1> p[UC][DIM];
 #pragma unroll
@@ -588,7 +662,7 @@ __global__ __launch_bounds__(256) void chain_tiny_kernel(const ChainArgs<T> A, c
     int64_t r[DIM];
 #pragma unroll
     for (int u = 0; u < DIM; ++u) r[u] = u;
-    const T l = apply_chain<T, 1, DIM, ROWMODE>(A, p[k], r, DIM);
+    const T l = apply_chain<T, 1, DIM, ROWMODE>(A, P, p[k], r, DIM);
     if (col < batch) {
       if (y) {
         TinyCol<T, DIM> t;
@@ -613,6 +687,7 @@ template <class T, int V, int ROWMODE, bool NT, int U>
 __global__ __launch_bounds__(256) void chain_colbatch_kernel(const ChainArgs<T> A, const T* x, T* y, T* ladj_ps, int64_t dim, int64_t batch, int G,
                                                              double c_ps_host, const double* c_ps_dev, int accumulate, double* partials) {
   __shared__ double red[4];
+  const ProgRegs<T> P = load_prog<T, ROWMODE>(A);
   const int gl = threadIdx.x & (G - 1);
   const int cols_per_block = 256 / G;
   const int64_t col0 = (int64_t)blockIdx.x * cols_per_block * U + threadIdx.x / G;
@@ -631,7 +706,7 @@ __global__ __launch_bounds__(256) void chain_colbatch_kernel(const ChainArgs<T> 
     }
   }
   T lu[U];
-  apply_chain_u<T, V, U, ROWMODE, true>(A, p, r, dim, lu);
+  apply_chain_u<T, V, U, ROWMODE, true>(A, P, p, r, dim, lu);
   // column heights that are not whole packs: the packs above are then only element-aligned, and the last dim % V rows go to the
   // lanes after the last pack's, ONE row each (all U columns at once: the same loads-in-flight as the packs; one lane walking the
   // three tail rows of four columns one after the other held dim = 63 / 127 / 255 at 26 %)
@@ -652,7 +727,7 @@ __global__ __launch_bounds__(256) void chain_colbatch_kernel(const ChainArgs<T> 
         pt[u].v[0] = (has_tail && col < batch) ? x[col * dim + rt[u]] : T(1);
       }
       T lt[U];
-      apply_chain_u<T, 1, U, (ROWMODE == 0 ? 0 : 2), true>(A, pt, rt, dim, lt);
+      apply_chain_u<T, 1, U, (ROWMODE == 0 ? 0 : 2), true>(A, P, pt, rt, dim, lt);
 #pragma unroll
       for (int u = 0; u < U; ++u) {
         const int64_t col = col0 + (int64_t)u * cols_per_block;
@@ -751,6 +826,24 @@ int chain_impl(bjx_ctx* ctx, const bjx_op* ops, int n_ops, const T* x, T* y, T* 
       }
     }
   }
+  if (!any_row) {
+    // the resolved program of the ROWMODE 0 kernels (same values, same stage order: nothing is folded)
+    ScalarProg<T>& sp = A.sp;
+    for (int k = 0; k < n_ops; ++k) {
+      const DevOp<T>& d = A.ops[k];
+      sp.kinds |= (uint32_t)d.kind << (4 * k);
+      memcpy(&sp.a[k], &d.s0, sizeof(T));
+      memcpy(&sp.b[k], &d.s1, sizeof(T));
+      if (d.plen == 1 && d.v0) sp.dev |= 1u << (2 * k);
+      if (d.plen == 1 && d.v1) sp.dev |= 1u << (2 * k + 1);
+    }
+    if (sp.dev) {
+      for (int k = 0; k < BJX_MAX_OPS; ++k) {
+        sp.va[k] = (sp.dev >> (2 * k)) & 1u ? A.ops[k].v0 : reinterpret_cast<const T*>(ctx->consts);
+        sp.vb[k] = (sp.dev >> (2 * k + 1)) & 1u ? A.ops[k].v1 : reinterpret_cast<const T*>(ctx->consts);
+      }
+    }
+  }
   const int64_t n = dim * batch;
   if (n == 0) {
     if (ladj_sum && !(flags & BJX_ACCUMULATE)) BJX_HIP(ctx, hipMemsetAsync(ladj_sum, 0, sizeof(double), ctx->stream));
@@ -797,12 +890,16 @@ int chain_impl(bjx_ctx* ctx, const bjx_op* ops, int n_ops, const T* x, T* y, T* 
     return BJX_OK;
   }
 
-  // Packs per thread (measured on MI355X, profiles/r01_chain_tuning.txt): a wave lives for one memory
-  // round trip, so its compute latency must be amortised over enough bytes in flight.  1 light
-  // stage: 2 packs (6.3 TB/s vs 5.9 with 1 / 5.7 with 4); anything heavier: 4 packs
-  // (C2 6.1 TB/s, C2 with per-row vectors 5.8 vs 5.0 with 2).
-  static const int tune_u = 0;
-  const int upt = tune_u ? tune_u : ((n_ops <= 1 && !any_row) ? 2 : 4);
+  // Packs per thread (measured on MI355X): a wave lives for one memory round trip, so its compute latency must be amortised over
+  // enough bytes in flight.  Scalar-only chains run as a resolved program (run_prog) and pay nothing per stage but ALU work; same
+  // call, alternating libraries, kernel ms at 64 x 2^24 (profiles/r07_chain_scalar_program.md): Float32 C2 1.660 / 1.335 / 1.390
+  // with 1 / 2 / 4 packs (the descriptor loop: 1.405 with 4) -> 2 packs; Float64 C2 2.18 / 1.67 / 1.48 (before: 1.62) -> 4 packs.
+  // Per-row parameters (profiles/r01_chain_tuning.txt): 4 packs (C2 with per-row vectors 5.8 TB/s vs 5.0 with 2).
+#ifndef BJX_CHAIN_TUNE_U
+#define BJX_CHAIN_TUNE_U 0      // -DBJX_CHAIN_TUNE_U=1|2|4: that many packs per thread for every flat launch (tuning builds); 0: the rule below
+#endif
+  static const int tune_u = BJX_CHAIN_TUNE_U;
+  const int upt = tune_u ? tune_u : ((!any_row && (n_ops <= 1 || sizeof(T) == 4)) ? 2 : 4);
 #define LAUNCH_FLAT_UV(V_, RM_, U_)                                                                           \
   do {                                                                                                        \
     grid = (n / V_ + 1 + 256 * U_ - 1) / (256 * U_);   /* +1: the lane that owns the n % V tail */            \
