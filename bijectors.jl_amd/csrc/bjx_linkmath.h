@@ -17,6 +17,15 @@ template <> struct LinkMath<float> {
     y = 0.5f * F::log((1.0f + w) * F::rcp(1.0f - w));
     lc = -0.5f * F::log((1.0f - w) * (1.0f + w));                            // logcosh(atanh w) = -log(1 - w^2)/2
   }
+  // atanh_lc with y good to a few ulp of ITSELF at both ends: log((1+w)/(1-w)) above is good to an ulp of 1, which at K = 2 — the sample's
+  // only entry — is 1e-2 of y at |y| = 3e-6.  Evaluated on a = |w| with the sign restored (odd in w to the bit): near 0 log1p keeps the
+  // ulp of its small argument, and towards 1 the difference 1 - a is exact (a >= 0.5), so 2a/(1-a) and its logarithm carry a few ulp.
+  // (On w itself the form fails for w -> -1: 2w/(1-w) -> -1 + d/2 is rounded to an ulp of 1 and 1 + x = d/2 loses e^{2|y|} of it.)
+  static __device__ __forceinline__ void atanh_lc_rel(float w, float& y, float& lc) {
+    const float a = fabsf(w);
+    y = __builtin_copysignf(0.5f * F::log1p((a + a) * F::rcp(1.0f - a)), w);
+    lc = -0.5f * F::log((1.0f - w) * (1.0f + w));
+  }
   // z = tanh(y), lc = logcosh(y) from one exp (LogExpFunctions.logcosh: |y| + log1pexp(-2|y|) - log 2)
   static __device__ __forceinline__ void tanh_lc(float y, float& z, float& lc) {
     const float ay = fabsf(y);
@@ -63,6 +72,7 @@ template <> struct LinkMath<double> {
     y = x_atanh(w);
     lc = -0.5 * F::log1p(-w * w);
   }
+  static __device__ __forceinline__ void atanh_lc_rel(double w, double& y, double& lc) { atanh_lc(w, y, lc); }
   static __device__ __forceinline__ void tanh_lc(double y, double& z, double& lc) {
     z = x_tanh(y);
     lc = f_logcosh(y);

@@ -1119,7 +1119,7 @@ __global__ __launch_bounds__(64) void chol_lane_kernel(const T* __restrict__ in,
           yo[i] = y;
         }
         T y0, lc0;
-        M::atanh_lc(col[0], y0, lc0);                              // :322
+        M::atanh_lc_rel(col[0], y0, lc0);                          // :322 (at K = 2 this entry is the whole sample)
         lsum += T(c + 1) * lc0;
         yo[0] = y0;
       }
@@ -2775,6 +2775,17 @@ __global__ __launch_bounds__(64) void chol_inv_vjp_lane_kernel(const T* __restri
       T* sc = my + nv;
       const T* dw = tw + lane * Pw;
       const T lb = lbar ? lbar[s0 + lane] : T(0);
+      // Float32, K = 2: a precision upgrade, not a repair.  The sample is ONE number, the sum (1 − z²)·ΔW[1,2] − z·(W[2,2]·ΔW[2,2] + 2·ΔlogJ) of
+      // two terms of either sign; any Float32 evaluation (the reference's own included) leaves an ulp of the TERMS on it, which among a
+      // million samples is up to 1e-1 of a value that has cancelled.  In Float64 the result is good to an ulp of itself; at 28 bytes per
+      // sample the kernel stays memory-bound.  From K = 3 on a sample has several entries and is measured on its largest.
+      if (sizeof(T) == 4 && K == 2) {
+        using MD = LinkMath<double>;
+        double z, lc;
+        MD::tanh_lc((double)my[0], z, lc);
+        const double dlr = MD::exp(-lc) * (double)dw[3] + 2.0 * (double)lb;
+        my[0] = (T)((1.0 - z * z) * (double)(lower ? dw[1] : dw[2]) - z * dlr);
+      } else
       for (int j = 1; j < K; ++j) {
         T* yj = my + j * (j - 1) / 2;
         T lr = T(0);
