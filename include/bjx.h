@@ -201,7 +201,9 @@ int bjx_vec_cholesky(bjx_ctx* ctx, bjx_dtype dt, int inverse, int uplo, const vo
 
 /* ------------------------------- matrix-variate constraint bijectors (per-sample Cholesky) */
 /* What bijector(::LKJ) / bijector(::Wishart-family) return.  X is a dense K x K column-major matrix per sample
- * (X[K,K,batch]); K <= 64 (one wave per sample, the factor's rows in registers; larger K -> BJX_ERR_UNSUPPORTED).
+ * (X[K,K,batch]); K <= 64: register-resident kernels (one lane per sample to K = 12, then the factor's rows spread
+ * cyclically over a wave); 65 <= K <= 1024: one block per sample on a global workspace, serial pivots (correct, not
+ * fast); K > 1024 -> BJX_ERR_UNSUPPORTED.
  * The triangle of X that is READ is the one the reference's Cholesky wrapper reads (src/utils.jl:37,50):
  * the UPPER one for the correlation bijectors (cholesky(Hermitian(X)).U), the LOWER one for the PD bijectors
  * (cholesky(Hermitian(X, :L)).L).  The inverse writes the full symmetric matrix (pd_from_upper / pd_from_lower,
@@ -239,8 +241,12 @@ int bjx_pd_vec(bjx_ctx* ctx, bjx_dtype dt, int inverse, const void* in, void* ou
  * inverse=0 (matrix -> unconstrained): in = X dense, out_bar = ȳ in the layout of the forward output, in_bar = X̄ dense; the
  *   cotangent of the link (corr.jl:299-335, pd.jl:11) goes through the reverse of cholesky(Hermitian(X)) and lands on the
  *   triangle the reference READS (upper for the correlation bijectors, src/utils.jl:50; lower for PD, :37) — the other
- *   triangle of X̄ is zero.  in_bar may alias in.  K <= 12: one lane per sample, factor and cotangent in registers; larger K:
- *   the same code on a global workspace (correct, not fast). */
+ *   triangle of X̄ is zero.  in_bar may alias in (the same pointer).
+ * K <= 8: one lane per sample, factor and cotangent in registers.  9 <= K <= 64: one group of 16 / 32 / 64 lanes per sample
+ *   with the factor in LDS — inverse=1 on the matrix cores in persistent blocks; inverse=0 on the matrix cores at K = 13..16
+ *   and from 25 rows (Float64: from 25), the lane = row group kernel at the other sizes.  65 <= K <= 1024: the one-lane code
+ *   on a global workspace (correct, not fast).  K > 1024 -> BJX_ERR_UNSUPPORTED.  K = 1 of bjx_vec_corr_vjp has no free
+ *   parameter: inverse=1 touches nothing, inverse=0 takes out_bar = NULL and writes a zero X̄. */
 int bjx_vec_corr_vjp(bjx_ctx* ctx, bjx_dtype dt, int inverse, const void* in, const void* out_bar, const void* ladj_bar,
                      void* in_bar, int64_t K, int64_t batch);
 int bjx_corr_vjp(bjx_ctx* ctx, bjx_dtype dt, int inverse, const void* in, const void* out_bar, const void* ladj_bar,
