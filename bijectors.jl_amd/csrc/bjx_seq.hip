@@ -247,7 +247,7 @@ template <class T, class Op>
 int launch_seq_chunk(bjx_ctx* ctx, const Op& op, const T* in, T* out, T* ladj_ps, double* ladj_sum, int64_t rows_in, int64_t rows_out,
                      int64_t batch, int n_logk, uint32_t flags, int64_t ld_in, int64_t ld_out) {
   constexpr int C = 256 / (int)sizeof(T), VW = Vec16<T>::N;
-  const bool table = (size_t)n_logk * sizeof(T) <= 40 * 1024;                  // taller: log(K-1-i) on the fly
+  const bool table = (size_t)n_logk * sizeof(T) <= 40 * 1024;                  // taller: log(K-1-i) on the fly; this, the 2 GiB limit and v_ok (restated in tests/_seq_ref.py: change both)
   const size_t smem = ((size_t)64 * (C + 1) + (table ? (size_t)n_logk : 1)) * sizeof(T);
   BJX_REQUIRE(ctx, (int64_t)64 * (ld_in > ld_out ? ld_in : ld_out) * (int64_t)sizeof(T) < ((int64_t)1 << 31), BJX_ERR_UNSUPPORTED,
               "columns of %lld elements: a wave's 64 columns exceed the 2 GiB range of one buffer descriptor", (long long)(ld_in > ld_out ? ld_in : ld_out));
@@ -290,7 +290,7 @@ int launch_seq(bjx_ctx* ctx, const Op& op, const T* in, T* out, T* ladj_ps, doub
     // (same-box A/B, profiles/r03_tall_columns.md: the chunk loads are runs of 256 bytes that straddle cache lines, so part of
     //  every line is fetched twice — the chunked walker wins only where the whole-column tile leaves < 3 waves per CU:
     //  K = 100: 30 % against 49 %, 200: 29-34 % against 27-31 %, 256: 39-68 % against 35-61 %, 1000: 34-41 % (no tile at all))
-    static const long chunk_min = 50 * 1024;
+    static const long chunk_min = 50 * 1024;                             // (restated in tests/_seq_ref.py: change both), as is v_ok below
     if (smem_w > (size_t)chunk_min && rows_in >= 1 && rows_out >= 1)
       return launch_seq_chunk<T, Op>(ctx, op, in, out, ladj_ps, ladj_sum, rows_in, rows_out, batch, n_logk, flags, ld_in, ld_out);
     if (use_wave && smem_w <= 64 * 1024 && rows_in >= 1 && rows_out >= 1) {   // larger columns: the chunked block kernel below
@@ -1555,7 +1555,7 @@ int ordered_vjp_impl(bjx_ctx* ctx, int inverse, const T* in, const T* out_bar, c
     constexpr int VW = Vec16<T>::N;
     static const int use_stream = getenv("BJX_ORDERED_VJP_STREAM") ? atoi(getenv("BJX_ORDERED_VJP_STREAM")) : 1;
     const int64_t packs = (dim + VW - 1) / VW;
-    if (use_stream && dim >= 2 * VW && packs <= 64 * 8) {
+    if (use_stream && dim >= 2 * VW && packs <= 64 * 8) {               // this range, G, R, uc and the branches below (restated in tests/_seq_ref.py: change both)
       // whole aligned packs or not: 16-byte packs on element-aligned addresses, a partial last pack, R packs per lane beyond 64
       int G = 1;
       while (G < 64 && G < packs) G <<= 1;
@@ -1942,7 +1942,7 @@ int simplex_vjp_impl(bjx_ctx* ctx, int inverse, const T* in, const T* out_bar, c
   // tall columns: the chunked two-pass kernel (two whole-column tiles of 64 columns cost 2·64·K words: beyond `chunk_min` bytes
   // the whole-column kernel runs with too few waves, then with too few lanes)
   // (K = 100: 22 / 13 % against 29 / 23 % for the whole-column kernel; K = 200: 24 / 13 % against 11 / 9 %; K = 500: 24 / 14 % against 6 / 5 %)
-  static const long vjp_chunk_min = 80 * 1024;
+  static const long vjp_chunk_min = 80 * 1024;                         // this, `table`, the 2 GiB limit and the order of the kernels above (restated in tests/_seq_ref.py: change both)
   if (((size_t)2 * 64 * (K | 1) + (size_t)K) * sizeof(T) > (size_t)vjp_chunk_min) {
     constexpr int CH = 128 / (int)sizeof(T);
     const bool table = (size_t)K * sizeof(T) <= 40 * 1024;
@@ -1987,6 +1987,9 @@ BJX_API int bjx_simplex_vjp(bjx_ctx* ctx, bjx_dtype dt, int inverse, const void*
   BJX_REQUIRE(ctx, K > 1, BJX_ERR_SHAPE, "bjx_simplex_vjp: x needs to be of length greater than 1 (simplex.jl:30), got K=%lld", (long long)K);
   BJX_REQUIRE(ctx, batch >= 0, BJX_ERR_SHAPE, "bjx_simplex_vjp: negative batch");
   BJX_REQUIRE(ctx, (in && out_bar && in_bar) || batch == 0, BJX_ERR_ARG, "bjx_simplex_vjp: null pointer");
+  // in_bar has the rows of `in`, out_bar one more or one fewer: column c of the one overlaps columns c - 1, c of the other, which another
+  // lane, wave or block may not have read yet — no kernel of this family orders its stores behind another column's loads
+  BJX_REQUIRE(ctx, (const void*)in_bar != out_bar || batch == 0, BJX_ERR_ARG, "bjx_simplex_vjp: in_bar may not alias out_bar (their columns differ by one row)");
   if (dt == BJX_F32) return simplex_vjp_impl<float>(ctx, inverse, (const float*)in, (const float*)out_bar, (const float*)ladj_bar, (float*)in_bar, K, batch);
   if (dt == BJX_F64) return simplex_vjp_impl<double>(ctx, inverse, (const double*)in, (const double*)out_bar, (const double*)ladj_bar, (double*)in_bar, K, batch);
   return bjx_fail(ctx, BJX_ERR_ARG, "bjx_simplex_vjp: bad dtype %d", (int)dt);
@@ -2345,6 +2348,7 @@ int launch_quad_stream(bjx_ctx* ctx, const Op& op, const T* in, T* out, T* ladj_
   *taken = false;
   static const int use_stream = getenv("BJX_SEQ_STREAM") ? atoi(getenv("BJX_SEQ_STREAM")) : 1;
   const int64_t np = R / (G * VW);
+  // the conditions of this frame and H of QS below (restated in tests/_seq_ref.py: change both)
   constexpr int NPMAX = G >= 4 ? 8 : 16 / G;                 // four lanes per column: R <= 128 (Float32) / 64 (Float64), 32 rows per lane; fewer lanes: R <= 64 / 32
   if (!use_stream || batch <= 0 || R % (G * VW) != 0 || np < 1 || np > NPMAX || !bjx_aligned16(in) || (out && !bjx_aligned16(out))) return BJX_OK;
   if (np > 8 && np != 16) return BJX_OK;                     // np = 1 … 8 (every multiple of 16 rows up to 128 in Float32), 16
@@ -2626,6 +2630,7 @@ int launch_simplex_vjp_stream(bjx_ctx* ctx, int inverse, const T* in, const T* o
   static const int use_stream = getenv("BJX_SIMPLEX_VJP_STREAM") ? atoi(getenv("BJX_SIMPLEX_VJP_STREAM")) : 1;
   const int64_t np = K / (G * VW);
   constexpr int NPMAX = G >= 4 ? 8 : 16 / G;                  // four lanes per column: K <= 128 (Float32) / 64 (Float64)
+  // (restated in tests/_seq_ref.py: change both)
   if (!use_stream || batch <= 0 || K % (G * VW) != 0 || np < 1 || np > NPMAX || !bjx_aligned16(in) || !bjx_aligned16(out_bar) || !bjx_aligned16(in_bar)) return BJX_OK;
   *taken = true;
   const int64_t cpb = 4 * (64 / G);
@@ -2661,7 +2666,7 @@ int ordered_impl(bjx_ctx* ctx, int inverse, const T* in, T* out, T* ladj_ps, dou
     return launch_seq<T>(ctx, OrderedInv<T>{}, in, out, ladj_ps, ladj_sum, dim, dim, batch, 0, flags, ld_in, ld_out);
   }
   {
-    bool taken = false;                                                // 1 ... 7 rows: lane = column in registers (bjx_tiny.hip)
+    bool taken = false;                                                // 1 ... 8 rows: lane = column in registers (bjx_tiny.hip)
     const int rc = bjx_seq_tiny(ctx, sizeof(T) == 4 ? BJX_F32 : BJX_F64, inverse ? BJX_TALL_ORDERED_INV : BJX_TALL_ORDERED_FWD, in, out, ladj_ps, ladj_sum, dim,
                                 batch, flags, &taken);
     if (rc || taken) return rc;
@@ -2692,7 +2697,7 @@ int simplex_impl(bjx_ctx* ctx, int inverse, const T* in, T* out, T* ladj_ps, dou
   if (!strided) {
     bool taken = false;
     int rc = bjx_seq_tiny(ctx, sizeof(T) == 4 ? BJX_F32 : BJX_F64, inverse ? BJX_TALL_SIMPLEX_INV : BJX_TALL_SIMPLEX_FWD, in, out, ladj_ps, ladj_sum, K, batch,
-                          flags, &taken);                              // 2 ... 7 rows: lane = column in registers (bjx_tiny.hip)
+                          flags, &taken);                              // 2 ... 8 rows: lane = column in registers (bjx_tiny.hip)
     if (rc || taken) return rc;
     if (!inverse) rc = want ? launch_quad_stream<T>(ctx, QSimplexFwd<T, true>{}, in, out, ladj_ps, ladj_sum, K, batch, flags, &taken)
                             : launch_quad_stream<T>(ctx, QSimplexFwd<T, false>{}, in, out, ladj_ps, ladj_sum, K, batch, flags, &taken);
@@ -2707,6 +2712,7 @@ int simplex_impl(bjx_ctx* ctx, int inverse, const T* in, T* out, T* ladj_ps, dou
         rc = want ? launch_quad_stream<T>(ctx, QSimplexInv<T, true, 1>{}, in, out, ladj_ps, ladj_sum, K, batch, flags, &taken)
                   : launch_quad_stream<T>(ctx, QSimplexInv<T, false, 1>{}, in, out, ladj_ps, ladj_sum, K, batch, flags, &taken);
       if (rc || taken) return rc;
+      // which frame the inverse takes (restated in tests/_seq_ref.py: change both)
       if (g4 || K % (2 * VWq) != 0 || K / (2 * VWq) > 8 || (K / (2 * VWq) > 4 && K / (2 * VWq) != 8))
         rc = want ? launch_quad_stream<T>(ctx, QSimplexInv<T, true, 4>{}, in, out, ladj_ps, ladj_sum, K, batch, flags, &taken)
                   : launch_quad_stream<T>(ctx, QSimplexInv<T, false, 4>{}, in, out, ladj_ps, ladj_sum, K, batch, flags, &taken);

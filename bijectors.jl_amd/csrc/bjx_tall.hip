@@ -855,6 +855,7 @@ int bjx_tall_stream(bjx_ctx* ctx, bjx_dtype dt, int which, const void* in, void*
   *taken = false;
   static const int use_tall = getenv("BJX_SEQ_TALL") ? atoi(getenv("BJX_SEQ_TALL")) : 1;
   // the Simplex inverse pays four chain operations per row and round: beyond `inv_max` rows the chunked walker is ahead (same-box A/B)
+  // every height condition of this function, `eff`, nsteps and vin / vout of launch_tall (restated in tests/_seq_ref.py: change both)
   static const long inv_max = 512;
   static const long min_rows = 65;
   const int rpl = dt == BJX_F32 ? 32 : 16;
@@ -889,6 +890,7 @@ int bjx_tall_simplex_vjp(bjx_ctx* ctx, bjx_dtype dt, int inverse, const void* in
                          int64_t batch, bool* taken) {
   *taken = false;
   static const int use_tall = getenv("BJX_SIMPLEX_VJP_TALL") ? atoi(getenv("BJX_SIMPLEX_VJP_TALL")) : 1;
+  // these conditions, nsteps and vk / vk1 of launch_tall_simplex_vjp (restated in tests/_seq_ref.py: change both)
   static const long min_rows = 65;
   static const long inv_max = 2048;
   const int rpl = dt == BJX_F32 ? 32 : 16;

@@ -242,6 +242,7 @@ int tiny_vjp_dispatch(bjx_ctx* ctx, int simplex, int inverse, int K, const T* in
 }  // namespace
 
 // Pullbacks of the Ordered (simplex = 0) / Simplex (simplex = 1) maps on columns of K <= 8 rows; *taken as above
+// kmax and the step aside at in == in_bar, here and in bjx_seq_tiny, (restated in tests/_seq_ref.py: change both)
 int bjx_seq_tiny_vjp(bjx_ctx* ctx, bjx_dtype dt, int simplex, int inverse, const void* in, const void* out_bar, const void* ladj_bar, void* in_bar, int64_t K,
                      int64_t batch, bool* taken) {
   *taken = false;

@@ -542,9 +542,13 @@ int bjx_stacked_mixed(bjx_ctx* ctx, bjx_dtype dt, const bjx_segment* segs, int n
  *     in_bar = J(in)^T * out_bar + ladj_bar * grad_in logabsdetjac
  * `in` is the PRIMAL INPUT of the direction being differentiated, `out_bar` the cotangent of its
  * output (same shape), `ladj_bar` the cotangent of the per-sample log-det (T[batch], may be NULL = 0),
- * `in_bar` the result (may not alias `in`; may alias `out_bar`).
+ * `in_bar` the result.  Aliasing: bjx_ordered_vjp and bjx_simplex_vjp each state below what in_bar may alias, and refuse the alias
+ * they do not serve with BJX_ERR_ARG before anything is launched or written; bjx_stacked_vjp and bjx_stacked_vjp_moments refuse
+ * x_bar == x the same way.  The two VecCholesky pullbacks check nothing: their result may alias neither input.
  * OrderedBijector: ext/BijectorsChainRulesCoreExt.jl:65-197 (rrules of _transform_ordered and
- * _transform_inverse_ordered, matrix methods). */
+ * _transform_inverse_ordered, matrix methods).  bjx_ordered_vjp: in_bar may alias `in` (the same pointer) at every height — the
+ * result has the bits of the out-of-place call; it may alias `out_bar` up to 2 048 (Float32) / 1 024 (Float64) rows and is refused
+ * (BJX_ERR_ARG) on taller columns, whose kernels read a neighbouring row's cotangent after it has been overwritten. */
 /* Stacked / any chain of elementwise bijectors (same segment list as bjx_stacked): x_bar[src row] =
  * (dy/dx) y_bar[out row] + ladj_bar (d logabsdetjac / dx), element by element (the Jacobian is diagonal up
  * to the row mapping).  Gradients with respect to the bijectors' PARAMETERS are not produced. */
@@ -564,20 +568,22 @@ int bjx_ordered_vjp(bjx_ctx* ctx, bjx_dtype dt, int inverse, const void* in, con
 /* SimplexBijector (K = rows of the simplex side): reverse sweeps of simplex.jl:47-64 / :102-120 and of the
  * log-det terms :122-138 (the reference's adjoints: simplex.jl:145-215, :248-308, :358-470).
  * inverse=1: in = y[K-1,batch], out_bar = x_bar[K,batch], in_bar = y_bar[K-1,batch];
- * inverse=0: in = x[K,batch],   out_bar = y_bar[K-1,batch], in_bar = x_bar[K,batch]. */
+ * inverse=0: in = x[K,batch],   out_bar = y_bar[K-1,batch], in_bar = x_bar[K,batch].
+ * in_bar may alias `in` (the same pointer; the bits of the out-of-place call).  It may NOT alias out_bar (BJX_ERR_ARG): their columns
+ * differ by one row, so a column of the one lies over parts of two columns of the other. */
 int bjx_simplex_vjp(bjx_ctx* ctx, bjx_dtype dt, int inverse, const void* in, const void* out_bar,
                     const void* ladj_bar, void* in_bar, int64_t K, int64_t batch);
 /* VecCholeskyBijector forward link W[K,K,batch] -> y[n,batch]: the rule the reference ships for
  * _link_chol_lkj_from_upper / _from_lower (ext/BijectorsChainRulesCoreExt.jl:199-311).  It lives on the constraint
  * manifold of Cholesky factors of correlation matrices (unit-norm columns): W_bar[j,j] = 0 and the entries outside
  * the strict triangle — undefined in the reference — are written as zeros.  No log-det cotangent: the reference's
- * rule covers the link only. */
+ * rule covers the link only.  W_bar may alias neither W nor y_bar (not checked). */
 int bjx_vec_cholesky_fwd_vjp(bjx_ctx* ctx, bjx_dtype dt, int uplo, const void* W, const void* y_bar,
                              void* W_bar, int64_t K, int64_t batch);
 /* inverse(VecCholeskyBijector): y[n,batch] -> (W[K,K,batch], logJ[batch]); pullback
  * src/bijectors/corr.jl:402-451 (_inv_link_chol_lkj_rrule; ext/BijectorsChainRulesCoreExt.jl:311-320).
  * W_bar: dense K x K per sample (entries outside the stored triangle are ignored), logJ_bar: T[batch]
- * or NULL, y_bar: T[n,batch]. */
+ * or NULL, y_bar: T[n,batch]; y_bar may alias neither y nor W_bar (not checked). */
 int bjx_vec_cholesky_inv_vjp(bjx_ctx* ctx, bjx_dtype dt, int uplo, const void* y, const void* W_bar,
                              const void* logJ_bar, void* y_bar, int64_t K, int64_t batch);
 

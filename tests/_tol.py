@@ -112,8 +112,8 @@ def flat_close(got, ref, dt, what, per="sample", term_scale=None, floor=0.0, not
                   f"first-order amplification {cond[worst]:.3g} (max over columns {cond.max():.3g}); bar = max(rtol, {COND_C:g}·amplification)")
     if term_scale is not None:
         rec["term_scale"] = float(np.max(term_scale))
-    if floor:
-        rec["floor"] = float(floor)
+    if np.any(floor):                                   # a scalar, or (per="element") an array of the reference's shape
+        rec["floor"] = float(np.max(floor))
     if note:
         rec["note"] = note
     _record(rec)
