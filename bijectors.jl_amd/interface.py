@@ -547,82 +547,93 @@ def _fast_plans(on: bool = True) -> None:
     _FAST_OFF[0] = not on
 
 
-def _fast_build(owner, get_ops, x, dim, per_sample, key):
-    def not_applicable():                              # remembered too: the next call of this shape goes straight to the general path
-        fp = _FastPlan(None, _BIJ_EPOCH[0], None, None, False)
-        owner.__dict__.setdefault("_fast", {})[key] = fp
-        return fp
+def _plan_get(owner, key):
+    """The plan (or "not applicable" marker) kept on `owner` under `key`, None when there is none of the current epoch."""
+    cache = owner.__dict__.get("_fast")
+    fp = cache.get(key) if cache is not None else None
+    return fp if fp is not None and fp.epoch == _BIJ_EPOCH[0] else None
 
-    ops = get_ops()
-    if ops is None or len(ops) > L.BJX_MAX_OPS:
-        return not_applicable()
-    ops2 = get_ops()                                   # a parameter that is a TEMPORARY (e.g. the negated shift of an inverse) is a new tensor every time
-    for (k1, a0, a1), (k2, b0, b1) in zip(ops, ops2):
-        for p, q in ((a0, b0), (a1, b1)):
-            if isinstance(p, torch.Tensor) and p is not q:
-                return not_applicable()
-    if _chain_key(ops, x, dim) is None:                # host / other-dtype / broadcast parameters: the general path converts them per call
-        return not_applicable()
-    ctx = context(x.device)
-    arr = (L.BjxOp * max(len(ops), 1))()
-    keep = []
-    for i, (kind, p0, p1) in enumerate(ops):
-        o = arr[i]
-        o.kind, o.param_len, o.p0, o.p1, o.v0, o.v1 = kind, 0, 0.0, 0.0, None, None
-        for j, p in enumerate((p0, p1)):
-            if p is None:
-                continue
-            if isinstance(p, torch.Tensor) and p.dim() > 0 and p.numel() != 1:
-                keep.append(p)
-                o.param_len = dim
-                setattr(o, f"v{j}", p.data_ptr())
-            else:
-                o.param_len = max(o.param_len, 1)
-                setattr(o, f"p{j}", float(p))
-    flags = L.BJX_REF_VECTOR_SCALE_LADJ if per_sample is False else 0
-    h = C.c_void_p()
-    L.check(ctx.h, L.load().bjx_plan_chain(ctx.h, _dt(x), arr, len(ops), dim, flags, C.byref(h)), "bjx_plan_chain")
-    fp = _FastPlan(h, _BIJ_EPOCH[0], keep, ctx, x.dtype == torch.float32)
+
+def _plan_store(owner, key, h, keep, ctx, f32, cls=_FastPlan):
+    fp = cls(h, _BIJ_EPOCH[0], keep, ctx, f32)
     owner.__dict__.setdefault("_fast", {})[key] = fp
     return fp
 
 
+def _plan_na(owner, key, cls=_FastPlan):
+    """"Not applicable" is remembered too: the next call of this shape goes straight to the general path."""
+    return _plan_store(owner, key, None, None, None, False, cls)
+
+
+def _ops_stable(ops, ops2):
+    """Two builds of one op list hold the same tensors: a parameter that is a TEMPORARY (e.g. the negated shift of an inverse) is a new
+    tensor every time, and a plan must not keep its address."""
+    for (_, a0, a1), (_, b0, b1) in zip(ops, ops2):
+        for p, q in ((a0, b0), (a1, b1)):
+            if isinstance(p, torch.Tensor) and p is not q:
+                return False
+    return True
+
+
+def _dense_input(x):
+    """-> (nd, dim, batch) of a Float32 / Float64 vector or column-major matrix with rows, dense, on the current device; else None."""
+    nd = x.dim()
+    if nd == 2:
+        dim, batch = x.shape
+        if x.stride(0) != 1 or (batch > 1 and x.stride(1) != dim) or dim == 0:
+            return None
+    elif nd == 1:
+        dim, batch = x.shape[0], 1
+        if x.stride(0) != 1 or dim == 0:
+            return None
+    else:
+        return None
+    dt = x.dtype
+    if (dt is not torch.float32 and dt is not torch.float64) or x.device.index != torch._C._cuda_getDevice():
+        return None
+    return nd, dim, batch
+
+
+def _fast_build(owner, get_ops, x, dim, per_sample, key):
+    ops = get_ops()
+    if ops is None or len(ops) > L.BJX_MAX_OPS or not _ops_stable(ops, get_ops()):
+        return _plan_na(owner, key)
+    if _chain_key(ops, x, dim) is None:                # host / other-dtype / broadcast parameters: the general path converts them per call
+        return _plan_na(owner, key)
+    ctx = context(x.device)
+    arr, keep = _marshal_ops(ops, x, dim)              # of a list with a key: kinds, scalars and the parameters' own addresses
+    flags = L.BJX_REF_VECTOR_SCALE_LADJ if per_sample is False else 0
+    h = C.c_void_p()
+    L.check(ctx.h, L.load().bjx_plan_chain(ctx.h, _dt(x), arr, len(ops), dim, flags, C.byref(h)), "bjx_plan_chain")
+    return _plan_store(owner, key, h, keep, ctx, x.dtype == torch.float32)
+
+
 def _fast_build_stacked(owner, get_ops, x, dim, per_sample, key):
     """A `Stacked` whose segments are all elementwise chains of <= 4 ops, same height in and out: one bjx_stacked launch (bjx_plan_stacked)."""
-    def not_applicable():
-        fp = _FastPlan(None, _BIJ_EPOCH[0], None, None, False)
-        owner.__dict__.setdefault("_fast", {})[key] = fp
-        return fp
-
     if dim != owner.length_in or owner.length_out != dim:
-        return not_applicable()
+        return _plan_na(owner, key)
     segs_ops = [_elementwise_ops(b) for b in owner.bs]
     if any(o is None or len(o) > L.BJX_MAX_SEG_OPS for o in segs_ops):
-        return not_applicable()
-    segs2 = [_elementwise_ops(b) for b in owner.bs]                    # parameters that are temporaries are new tensors every time
-    for o1, o2 in zip(segs_ops, segs2):
-        for (k1, a0, a1), (k2, b0, b1) in zip(o1, o2):
-            for p_, q_ in ((a0, b0), (a1, b1)):
-                if isinstance(p_, torch.Tensor) and p_ is not q_:
-                    return not_applicable()
+        return _plan_na(owner, key)
+    segs2 = [_elementwise_ops(b) for b in owner.bs]
+    if not all(_ops_stable(o1, o2) for o1, o2 in zip(segs_ops, segs2)):
+        return _plan_na(owner, key)
     arr, keep = owner._segments(segs_ops, list(range(len(owner.bs))), x)
     if keep:                                                           # converted / broadcast parameters: the general path makes them per call
-        return not_applicable()
+        return _plan_na(owner, key)
     params = [p_ for o in segs_ops for (_, a0, a1) in o for p_ in (a0, a1) if isinstance(p_, torch.Tensor)]
     ctx = context(x.device)
     h = C.c_void_p()
     rc = L.load().bjx_plan_stacked(ctx.h, _dt(x), arr, len(owner.bs), dim, 0, C.byref(h))
     L.check(ctx.h, rc, "bjx_plan_stacked")
-    fp = _FastPlan(h, _BIJ_EPOCH[0], params + [arr], ctx, x.dtype == torch.float32)
-    owner.__dict__.setdefault("_fast", {})[key] = fp
-    return fp
+    return _plan_store(owner, key, h, params + [arr], ctx, x.dtype == torch.float32)
 
 
 def _fast_chain(owner, get_ops, x, per_sample, build=None):
     """-> (y, ladj) through a cached bjx_plan, or None when this call does not qualify (then the general path runs)."""
     if _FAST_OFF[0] or not isinstance(x, torch.Tensor) or not x.is_cuda or _OUT_HINT:
         return None
-    nd = x.dim()
+    nd = x.dim()                                        # `_dense_input` and `batch > 0`, inline: the call costs 0.2-0.3 us of this entry's 9.5 us
     if nd == 2:
         dim, batch = x.shape
         if x.stride(0) != 1 or (batch > 1 and x.stride(1) != dim) or dim == 0 or batch == 0:
@@ -640,9 +651,8 @@ def _fast_chain(owner, get_ops, x, per_sample, build=None):
     if dev != torch._C._cuda_getDevice():
         return None
     key = (dt, dim, per_sample, dev, torch._C._cuda_getCurrentRawStream(dev))
-    cache = owner.__dict__.get("_fast")
-    fp = cache.get(key) if cache is not None else None
-    if fp is None or fp.epoch != _BIJ_EPOCH[0]:
+    fp = _plan_get(owner, key)
+    if fp is None:
         fp = (build or _fast_build)(owner, get_ops, x, dim, per_sample, key)
     if fp.h is None:
         return None
@@ -669,44 +679,18 @@ def _fast_chain(owner, get_ops, x, per_sample, build=None):
 
 
 def _fast_vjp_build(owner, get_ops, x, dim, key):
-    def not_applicable():
-        fp = _FastPlan(None, _BIJ_EPOCH[0], None, None, False)
-        owner.__dict__.setdefault("_fast", {})[key] = fp
-        return fp
-
     ops = get_ops()
-    if ops is None or len(ops) > L.BJX_MAX_SEG_OPS:
-        return not_applicable()
-    ops2 = get_ops()
-    for (k1, a0, a1), (k2, b0, b1) in zip(ops, ops2):
-        for p, q in ((a0, b0), (a1, b1)):
-            if isinstance(p, torch.Tensor) and p is not q:
-                return not_applicable()
+    if ops is None or len(ops) > L.BJX_MAX_SEG_OPS or not _ops_stable(ops, get_ops()):
+        return _plan_na(owner, key)
     if _chain_key(ops, x, dim) is None:
-        return not_applicable()
+        return _plan_na(owner, key)
     ctx = context(x.device)
     seg = (L.BjxSegment * 1)()
-    sg = seg[0]
-    sg.in_lo, sg.out_lo, sg.len, sg.n_ops = 0, 0, dim, len(ops)
     keep = []
-    for k, (kind, p0, p1) in enumerate(ops):
-        o = sg.ops[k]
-        o.kind, o.param_len, o.p0, o.p1, o.v0, o.v1 = kind, 0, 0.0, 0.0, None, None
-        for j, p in enumerate((p0, p1)):
-            if p is None:
-                continue
-            if isinstance(p, torch.Tensor) and p.dim() > 0 and p.numel() != 1:
-                keep.append(p)
-                o.param_len = dim
-                setattr(o, f"v{j}", p.data_ptr())
-            else:
-                o.param_len = max(o.param_len, 1)
-                setattr(o, f"p{j}", float(p))
+    _fill_segment(seg[0], 0, 0, dim, ops, x, keep)
     h = C.c_void_p()
     L.check(ctx.h, L.load().bjx_plan_stacked_vjp(ctx.h, _dt(x), seg, 1, dim, C.byref(h)), "bjx_plan_stacked_vjp")
-    fp = _FastPlan(h, _BIJ_EPOCH[0], keep, ctx, x.dtype == torch.float32)
-    owner.__dict__.setdefault("_fast", {})[key] = fp
-    return fp
+    return _plan_store(owner, key, h, keep, ctx, x.dtype == torch.float32)
 
 
 def _fast_chain_vjp(owner, get_ops, x, out_bar, ladj_bar):
@@ -715,29 +699,18 @@ def _fast_chain_vjp(owner, get_ops, x, out_bar, ladj_bar):
         return None
     if ladj_bar is not None and not isinstance(ladj_bar, torch.Tensor):
         return None                                     # a python number: the general path broadcasts it
-    nd = x.dim()
-    if nd == 2:
-        dim, batch = x.shape
-        if x.stride(0) != 1 or (batch > 1 and x.stride(1) != dim) or dim == 0 or batch == 0:
-            return None
-    elif nd == 1:
-        dim, batch = x.shape[0], 1
-        if x.stride(0) != 1 or dim == 0:
-            return None
-    else:
+    q = _dense_input(x)
+    if q is None or q[2] == 0:
         return None
-    dt = x.dtype
-    if (dt is not torch.float32 and dt is not torch.float64) or out_bar.dtype is not dt or out_bar.shape != x.shape or out_bar.stride() != x.stride() or out_bar.device != x.device:
+    nd, dim, batch = q
+    dt, dev = x.dtype, x.device.index
+    if out_bar.dtype is not dt or out_bar.shape != x.shape or out_bar.stride() != x.stride() or out_bar.device != x.device:
         return None
     if ladj_bar is not None and (ladj_bar.dtype is not dt or ladj_bar.dim() != 1 or ladj_bar.shape[0] != batch or ladj_bar.stride(0) != 1 or ladj_bar.device != x.device):
         return None
-    dev = x.device.index
-    if dev != torch._C._cuda_getDevice():
-        return None
     key = ("vjp", dt, dim, dev, torch._C._cuda_getCurrentRawStream(dev))
-    cache = owner.__dict__.get("_fast")
-    fp = cache.get(key) if cache is not None else None
-    if fp is None or fp.epoch != _BIJ_EPOCH[0]:
+    fp = _plan_get(owner, key)
+    if fp is None:
         fp = _fast_vjp_build(owner, get_ops, x, dim, key)
     if fp.h is None:
         return None
@@ -1133,6 +1106,50 @@ def _chain_key(ops, xc, dim):
     return tuple(key)
 
 
+def _cache_ops(key, arr):
+    if len(_CHAIN_OPS) >= 512:
+        _CHAIN_OPS.clear()
+    _CHAIN_OPS[key] = arr
+
+
+def _fill_op(o, kind, p0, p1, rows, like, keep, what="input with"):
+    """One bjx_op (include/bjx.h) from (kind, p0, p1): param_len 0 without a parameter, 1 with host scalars (p0 / p1), `rows` with one
+    device value per row (v0 / v1) — python sequences and tensors are converted to `like`'s dtype and device, a scalar next to a vector
+    is broadcast.  The device tensors are appended to `keep`: they must outlive the launch.  `what` words the error of a chain
+    ("input with") or of a Stacked segment ("a segment of")."""
+    o.kind, o.param_len, o.p0, o.p1, o.v0, o.v1 = kind, 0, 0.0, 0.0, None, None
+    seq = any(_is_seq(p) for p in (p0, p1) if p is not None)
+    for j, p in enumerate((p0, p1)):
+        if p is None:
+            continue
+        if seq:
+            t = _param(p, like).reshape(-1) if _is_seq(p) else torch.full((rows,), float(p), dtype=like.dtype, device=like.device)
+            if t.numel() != rows:
+                raise ValueError(f"DimensionMismatch: parameter of length {t.numel()} for {what} {rows} rows")
+            keep.append(t)
+            o.param_len = rows
+            setattr(o, f"v{j}", t.data_ptr())
+        else:
+            o.param_len = 1
+            setattr(o, f"p{j}", float(p))
+
+
+def _fill_segment(sg, in_lo, out_lo, rows, ops, like, keep):
+    """One bjx_segment: rows [in_lo, in_lo + rows) -> [out_lo, out_lo + rows) (0-based) through `ops`."""
+    sg.in_lo, sg.out_lo, sg.len, sg.n_ops = in_lo, out_lo, rows, len(ops)
+    for k, (kind, p0, p1) in enumerate(ops):
+        _fill_op(sg.ops[k], kind, p0, p1, rows, like, keep, "a segment of")
+
+
+def _marshal_ops(ops, like, rows):
+    """[(kind, p0, p1)] -> (ctypes bjx_op array, tensors to keep alive)."""
+    arr = (L.BjxOp * max(len(ops), 1))()
+    keep = []
+    for i, (kind, p0, p1) in enumerate(ops):
+        _fill_op(arr[i], kind, p0, p1, rows, like, keep)
+    return arr, keep
+
+
 def _run_chain(ops: Sequence, x: torch.Tensor, per_sample: bool, want_ladj: bool = True, out_y: Optional[torch.Tensor] = None, store: bool = True, flags: int = 0):
     """One bjx_chain launch.  ops: [(kind, p0, p1)] in application order.  store=False: the values are not
     written (log-det / log-density only: half the traffic)."""
@@ -1143,30 +1160,12 @@ def _run_chain(ops: Sequence, x: torch.Tensor, per_sample: bool, want_ladj: bool
     # parameters are device tensors of the input's dtype are kept (no temporaries to keep alive); the key holds their addresses, so a
     # parameter that moved is a different key, and a pointer is all the kept array holds — nothing that could go stale.
     ckey = _chain_key(ops, xc, dim)
-    hit = _CHAIN_OPS.get(ckey) if ckey is not None else None
-    arr = hit if hit is not None else (L.BjxOp * max(len(ops), 1))()
+    arr = _CHAIN_OPS.get(ckey) if ckey is not None else None
     keep = []
-    for i, (kind, p0, p1) in enumerate(() if hit is not None else ops):
-        o = arr[i]
-        o.kind, o.param_len, o.p0, o.p1, o.v0, o.v1 = kind, 0, 0.0, 0.0, None, None
-        seq = any(_is_seq(p) for p in (p0, p1) if p is not None)
-        for j, p in enumerate((p0, p1)):
-            if p is None:
-                continue
-            if seq:
-                t = _param(p, xc).reshape(-1) if _is_seq(p) else torch.full((dim,), float(p), dtype=xc.dtype, device=xc.device)
-                if t.numel() != dim:
-                    raise ValueError(f"DimensionMismatch: parameter of length {t.numel()} for input with {dim} rows")
-                keep.append(t)
-                o.param_len = dim
-                setattr(o, f"v{j}", t.data_ptr())
-            else:
-                o.param_len = 1
-                setattr(o, f"p{j}", float(p))
-    if hit is None and ckey is not None:
-        if len(_CHAIN_OPS) >= 512:
-            _CHAIN_OPS.clear()
-        _CHAIN_OPS[ckey] = arr
+    if arr is None:
+        arr, keep = _marshal_ops(ops, xc, dim)
+        if ckey is not None:
+            _cache_ops(ckey, arr)
     if not store:
         y = None
     elif out_y is None:
@@ -2561,29 +2560,9 @@ class Stacked(Transform):
         keep = []
         for si, i in enumerate(fused):
             (lo, hi), (olo, _) = self.ranges_in[i], self.ranges_out[i]
-            sg = arr[si]
-            sg.in_lo, sg.out_lo, sg.len, sg.n_ops = lo - 1, olo - 1, hi - lo + 1, len(segs_ops[i])
-            for k, (kind, p0, p1) in enumerate(segs_ops[i]):
-                o = sg.ops[k]
-                o.kind, o.param_len, o.p0, o.p1, o.v0, o.v1 = kind, 0, 0.0, 0.0, None, None
-                seq = any(_is_seq(p) for p in (p0, p1) if p is not None)
-                for j, p in enumerate((p0, p1)):
-                    if p is None:
-                        continue
-                    if seq:
-                        t = _param(p, xc).reshape(-1) if _is_seq(p) else torch.full((sg.len,), float(p), dtype=xc.dtype, device=xc.device)
-                        if t.numel() != sg.len:
-                            raise ValueError(f"DimensionMismatch: parameter of length {t.numel()} for a segment of {sg.len} rows")
-                        keep.append(t)
-                        o.param_len = sg.len
-                        setattr(o, f"v{j}", t.data_ptr())
-                    else:
-                        o.param_len = 1
-                        setattr(o, f"p{j}", float(p))
+            _fill_segment(arr[si], lo - 1, olo - 1, hi - lo + 1, segs_ops[i], xc, keep)
         if skey is not None:
-            if len(_CHAIN_OPS) >= 512:
-                _CHAIN_OPS.clear()
-            _CHAIN_OPS[skey] = arr
+            _cache_ops(skey, arr)
         return arr, keep
 
     def _vjp(self, x, out_bar, ladj_bar, moments=False):
@@ -2655,25 +2634,7 @@ class Stacked(Transform):
 
         def fill_segment(sg, i, x_off, y_off, keep):
             lo, hi = self.ranges_in[i]
-            ln, ops = hi - lo + 1, segs_ops[i]
-            sg.in_lo, sg.out_lo, sg.len, sg.n_ops = lo - 1 - x_off, self.ranges_out[i][0] - 1 - y_off, ln, len(ops)
-            for k, (kind, p0, p1) in enumerate(ops):
-                o = sg.ops[k]
-                o.kind, o.param_len, o.p0, o.p1, o.v0, o.v1 = kind, 0, 0.0, 0.0, None, None
-                seq = any(_is_seq(p) for p in (p0, p1) if p is not None)
-                for j, p in enumerate((p0, p1)):
-                    if p is None:
-                        continue
-                    if seq:
-                        t = _param(p, xc).reshape(-1) if _is_seq(p) else torch.full((ln,), float(p), dtype=xc.dtype, device=xc.device)
-                        if t.numel() != ln:
-                            raise ValueError(f"DimensionMismatch: parameter of length {t.numel()} for a segment of {ln} rows")
-                        keep.append(t)
-                        o.param_len = ln
-                        setattr(o, f"v{j}", t.data_ptr())
-                    else:
-                        o.param_len = 1
-                        setattr(o, f"p{j}", float(p))
+            _fill_segment(sg, lo - 1 - x_off, self.ranges_out[i][0] - 1 - y_off, hi - lo + 1, segs_ops[i], xc, keep)
 
         # ONE launch when a whole column fits the LDS tile of bjx_stacked_mixed (a lane walks its column: elementwise rows and
         # structured blocks in the same pass); taller columns: the window launches below
@@ -3375,27 +3336,22 @@ class _ParamsPlan(_FastPlan):
 
 
 def _vjp_params_build(owner, stages, x, dim, key):
-    def not_applicable():
-        fp = _ParamsPlan(None, _BIJ_EPOCH[0], None, None, False)
-        owner.__dict__.setdefault("_fast", {})[key] = fp
-        return fp
-
     global _VJP_PARAMS_KINDS
     if _VJP_PARAMS_KINDS is None:
         _VJP_PARAMS_KINDS = {L.OP_IDENTITY, L.OP_EXP, L.OP_LOG, L.OP_SHIFT, L.OP_SCALE, L.OP_SCALE_INV, L.OP_LOGIT, L.OP_LOGIT_INV, L.OP_LEAKY_RELU, L.OP_SIGNFLIP}
     if not stages or len(stages) > L.BJX_CHAIN_VJP_MAX_OPS:
-        return not_applicable()
+        return _plan_na(owner, key, _ParamsPlan)
     ops = []
     for st in stages:
         o = _stage_ops(st)
         if o is None or len(o) != 1 or o[0][0] not in _VJP_PARAMS_KINDS:
-            return not_applicable()
+            return _plan_na(owner, key, _ParamsPlan)
         # the plan holds POINTERS: a tensor in the op must be the stage's own attribute, not a value derived per call
         # (inverse(Shift) carries -a, inverse(LeakyReLU) 1/α: temporaries when the parameter is a tensor)
         own = vars(st.orig if isinstance(st, Inverse) else st).values()
         for p in o[0][1:]:
             if isinstance(p, torch.Tensor) and not any(p is v for v in own):
-                return not_applicable()
+                return _plan_na(owner, key, _ParamsPlan)
         ops.append(o[0])
     arr = (L.BjxOp * len(ops))()
     keep, slots, total, mask = [arr], [], 0, 0
@@ -3412,19 +3368,19 @@ def _vjp_params_build(owner, stages, x, dim, key):
                 lens.append((j, 1, None))
             elif isinstance(p, torch.Tensor):
                 if p.device != x.device or p.dtype != x.dtype or not p.is_contiguous() or p.dim() > 1:
-                    return not_applicable()
+                    return _plan_na(owner, key, _ParamsPlan)
                 if p.numel() != 1 and p.numel() != dim:
-                    return not_applicable()
+                    return _plan_na(owner, key, _ParamsPlan)
                 keep.append(p)
                 setattr(o, f"v{j}", p.data_ptr())
                 lens.append((j, p.numel(), tuple(p.shape)))
             else:
-                return not_applicable()                          # lists / tuples are converted per call by the general path
+                return _plan_na(owner, key, _ParamsPlan)      # lists / tuples are converted per call by the general path
         if not lens:
             continue
         plen = max(n for _, n, _ in lens)
         if any(shape is not None and n != plen for _, n, shape in lens):
-            return not_applicable()                              # a one-element tensor next to a per-row one
+            return _plan_na(owner, key, _ParamsPlan)      # a one-element tensor next to a per-row one
         o.param_len = plen
         for j, n, shape in lens:
             if j < len(names):
@@ -3433,13 +3389,12 @@ def _vjp_params_build(owner, stages, x, dim, key):
                 total += n_out
                 mask |= 1 << (2 * k + j)
     if not slots:
-        return not_applicable()
+        return _plan_na(owner, key, _ParamsPlan)
     ctx = context(x.device)
     h = C.c_void_p()
     L.check(ctx.h, L.load().bjx_plan_chain_vjp_params(ctx.h, _dt(x), arr, len(ops), mask, dim, C.byref(h)), "bjx_plan_chain_vjp_params")
-    fp = _ParamsPlan(h, _BIJ_EPOCH[0], keep, ctx, x.dtype == torch.float32)
+    fp = _plan_store(owner, key, h, keep, ctx, x.dtype == torch.float32, _ParamsPlan)
     fp.slots, fp.total, fp.n_stages = slots, total, len(stages)
-    owner.__dict__.setdefault("_fast", {})[key] = fp
     return fp
 
 
@@ -3452,23 +3407,20 @@ def _chain_vjp_params(b, stages, x, out_bar, ladj_bar):
     re-assign the attribute (`st.a = st.a`) after such a write, which bumps the epoch and rebuilds the plan."""
     if _FAST_OFF[0] or not isinstance(b, Transform) or not isinstance(x, torch.Tensor) or not x.is_cuda or x.dim() != 2 or not isinstance(out_bar, torch.Tensor):
         return None
-    dim, batch = x.shape
-    dt = x.dtype
-    if dim == 0 or x.stride(0) != 1 or (batch > 1 and x.stride(1) != dim) or (dt is not torch.float32 and dt is not torch.float64):
+    q = _dense_input(x)
+    if q is None:
         return None
+    _, dim, batch = q
+    dt, dev = x.dtype, x.device.index
     if out_bar.dtype is not dt or out_bar.shape != x.shape or out_bar.device != x.device or out_bar.stride(0) != 1 or (batch > 1 and out_bar.stride(1) != dim):
-        return None
-    dev = x.device.index
-    if dev != torch._C._cuda_getDevice():
         return None
     if ladj_bar is not None:
         if not isinstance(ladj_bar, torch.Tensor) or ladj_bar.dtype is not dt or ladj_bar.dim() != 1 or ladj_bar.shape[0] != batch or ladj_bar.device != x.device \
                 or (batch > 1 and ladj_bar.stride(0) != 1):
             ladj_bar = _ladj_bar(ladj_bar, batch, x)
     key = ("vjp_params", dt, dim, dev, torch._C._cuda_getCurrentRawStream(dev))
-    cache = b.__dict__.get("_fast")
-    fp = cache.get(key) if cache is not None else None
-    if fp is None or fp.epoch != _BIJ_EPOCH[0]:
+    fp = _plan_get(b, key)
+    if fp is None:
         fp = _vjp_params_build(b, stages, x, dim, key)
     if fp.h is None:
         return None
@@ -3858,30 +3810,6 @@ class TransformedDistribution:
 def transformed(dist, b=None):
     """src/transformed_distribution.jl:20-28"""
     return TransformedDistribution(dist, identity if b is None else b)
-
-
-def _marshal_ops(ops, xc, dim):
-    """[(kind, p0, p1)] -> (ctypes bjx_op array, tensors to keep alive): the marshalling of `_run_chain`, without its cache."""
-    arr = (L.BjxOp * max(len(ops), 1))()
-    keep = []
-    for i, (kind, p0, p1) in enumerate(ops):
-        o = arr[i]
-        o.kind, o.param_len, o.p0, o.p1, o.v0, o.v1 = kind, 0, 0.0, 0.0, None, None
-        seq = any(_is_seq(p) for p in (p0, p1) if p is not None)
-        for j, p in enumerate((p0, p1)):
-            if p is None:
-                continue
-            if seq:
-                t = _param(p, xc).reshape(-1) if _is_seq(p) else torch.full((dim,), float(p), dtype=xc.dtype, device=xc.device)
-                if t.numel() != dim:
-                    raise ValueError(f"DimensionMismatch: parameter of length {t.numel()} for input with {dim} rows")
-                keep.append(t)
-                o.param_len = dim
-                setattr(o, f"v{j}", t.data_ptr())
-            else:
-                o.param_len = 1
-                setattr(o, f"p{j}", float(p))
-    return arr, keep
 
 
 _MATRIX_CHAIN_KINDS = (L.OP_EXP, L.OP_LOG, L.OP_SHIFT, L.OP_SCALE, L.OP_SCALE_INV)
