@@ -196,6 +196,14 @@ SIGNATURES_PLANAR_LOGPDF = {
     "bjx_planar_logpdf_vjp_params": (_i, [_vp, _i, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64]),
 }
 
+# include/bjx_planar_cols.h (a PlanarLayer stack with one (w, u, b) per column): p_w, p_u, p_b, ld_w, ld_u, ld_b, n_layers, then the data
+# as bjx_planar / bjx_planar_vjp; the pullback ends with the per-column w_bar, u_bar, b_bar (any of them may be NULL)
+BJX_PLANAR_COLS_MAX_LAYERS = 64
+SIGNATURES_PLANAR_COLS = {
+    "bjx_planar_cols": (_i, [_vp, _i, _i, _vp, _vp, _vp, _i64, _i64, _i64, _i, _vp, _vp] + _tail),
+    "bjx_planar_cols_vjp": (_i, [_vp, _i, _i, _vp, _vp, _vp, _i64, _i64, _i64, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64]),
+}
+
 _lib = None
 
 
@@ -211,12 +219,13 @@ def load() -> C.CDLL:
         )
     lib = C.CDLL(LIB_PATH, mode=C.RTLD_GLOBAL)
     missing = [n for n in list(SIGNATURES) + list(SIGNATURES_COLS) + list(SIGNATURES_COUPLING) + list(SIGNATURES_CHAIN_VJP) + list(SIGNATURES_RADIAL_STACK)
-               + list(SIGNATURES_RADIAL_STACK_PARAMS) + list(SIGNATURES_RADIAL_STACK_LOGPDF) + list(SIGNATURES_PLANAR_LOGPDF) if not hasattr(lib, n)]
+               + list(SIGNATURES_RADIAL_STACK_PARAMS) + list(SIGNATURES_RADIAL_STACK_LOGPDF) + list(SIGNATURES_PLANAR_LOGPDF) + list(SIGNATURES_PLANAR_COLS)
+               if not hasattr(lib, n)]
     if missing:  # an incomplete ABI is a build error, not something to paper over
         raise ImportError(f"{LIB_PATH} does not export {missing}; rebuild it")
     for name, (res, args) in (list(SIGNATURES.items()) + list(SIGNATURES_COLS.items()) + list(SIGNATURES_COUPLING.items())
                               + list(SIGNATURES_CHAIN_VJP.items()) + list(SIGNATURES_RADIAL_STACK.items()) + list(SIGNATURES_RADIAL_STACK_PARAMS.items())
-                              + list(SIGNATURES_RADIAL_STACK_LOGPDF.items()) + list(SIGNATURES_PLANAR_LOGPDF.items())):
+                              + list(SIGNATURES_RADIAL_STACK_LOGPDF.items()) + list(SIGNATURES_PLANAR_LOGPDF.items()) + list(SIGNATURES_PLANAR_COLS.items())):
         fn = getattr(lib, name)
         fn.restype = res
         fn.argtypes = args

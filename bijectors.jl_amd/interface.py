@@ -30,7 +30,7 @@ from . import _lib as L
 __all__ = [
     "Transform", "Bijector", "Inverse", "ComposedFunction", "Elementwise", "elementwise", "exp", "log", "identity",
     "Shift", "Scale", "Logit", "LeakyReLU", "TruncatedBijector", "SignFlip", "OrderedBijector", "SimplexBijector",
-    "VecCholeskyBijector", "VecCorrBijector", "CorrBijector", "PDBijector", "PDVecBijector", "Permute", "PlanarLayer", "RadialLayer", "InvertibleBatchNorm", "RationalQuadraticSpline",
+    "VecCholeskyBijector", "VecCorrBijector", "CorrBijector", "PDBijector", "PDVecBijector", "Permute", "PlanarLayer", "AmortizedPlanarLayer", "RadialLayer", "InvertibleBatchNorm", "RationalQuadraticSpline",
     "PartitionMask", "Coupling", "Stacked", "NamedStacked", "Columnwise", "columnwise", "vjp", "istraining", "training", "transform", "inverse", "logabsdetjac", "with_logabsdet_jacobian",
     "with_logabsdet_jacobian_", "transform_", "output_size", "isinvertible", "isclosedform", "colmajor", "context", "_fast_plans",
     "PlanarResult", "vjp_params", "row_moments", "MvNormal", "TorchBase", "TransformedDistribution", "transformed", "logpdf", "logpdf_vjp_params", "rand",
@@ -444,7 +444,7 @@ def isinvertible(t) -> bool:  # interface.jl:238,273
 def isclosedform(t) -> bool:  # interface.jl:231 ; planar_layer.jl:188 ; composed.jl:2
     if isinstance(t, ComposedFunction):
         return isclosedform(t.inner) and isclosedform(t.outer)
-    if isinstance(t, Inverse) and isinstance(t.orig, PlanarLayer):
+    if isinstance(t, Inverse) and isinstance(t.orig, (PlanarLayer, AmortizedPlanarLayer)):
         return False
     return True
 
@@ -1644,6 +1644,101 @@ def _planned(stages):
         spans.append((i, j))
         i = j
     return out, spans
+
+
+class AmortizedPlanarLayer(Bijector):
+    """A stack of planar layers (planar_layer.jl:12-188) with one parameter set per COLUMN of the batch — the amortised flow of
+    Rezende & Mohamed (2015), where an encoder emits (w, u, b) for every sample (include/bjx_planar_cols.h).
+
+    `w`, `u`: (dim, batch) for one layer or (dim, n_layers, batch); `b`: (batch,) or (n_layers, batch).  Layers apply in the
+    order 0 … n_layers−1.  Tensors already laid out column-major per column — a `permute(2, 1, 0)` view of a (batch, n_layers, dim)
+    network output, or a slice of one head [2·dim·L + L, batch] — are passed with their column stride and no copy.  It is NOT
+    a PlanarLayer: the composition planner, the plans and the batch-summed parameter pullback leave it alone; `vjp_params`
+    returns the cotangents of w, u, b per column, with the shapes given here.  At most 64 layers; dim <= 1 024 in Float32 and
+    512 in Float64 (ValueError otherwise)."""
+
+    MAX_DIM = {torch.float32: 1024, torch.float64: 512}
+
+    def __init__(self, w, u, b):
+        self.w, self.u, self.b = torch.as_tensor(w), torch.as_tensor(u), torch.as_tensor(b)
+        if self.w.dim() not in (2, 3) or self.u.shape != self.w.shape:
+            raise ValueError("DimensionMismatch: expected w and u of the same shape (dim, batch) or (dim, n_layers, batch)")
+        self.n_layers = 1 if self.w.dim() == 2 else int(self.w.shape[1])
+        self.dim, self.batch = int(self.w.shape[0]), int(self.w.shape[-1])
+        if not 1 <= self.n_layers <= L.BJX_PLANAR_COLS_MAX_LAYERS:
+            raise ValueError(f"AmortizedPlanarLayer: {self.n_layers} layers (1 ... {L.BJX_PLANAR_COLS_MAX_LAYERS} supported)")
+        if tuple(self.b.shape) != (self.n_layers, self.batch) and not (self.n_layers == 1 and tuple(self.b.shape) == (self.batch,)):
+            raise ValueError(f"DimensionMismatch: expected b of shape ({self.n_layers}, {self.batch})" + (f" or ({self.batch},)" if self.n_layers == 1 else ""))
+
+    def _key(self):
+        return (_keyify(self.w), _keyify(self.u), _keyify(self.b))
+
+    def _col_params(self, like, dim, batch):
+        """-> (p_w, p_u, p_b, ld_w, ld_u, ld_b) for bjx_planar_cols: w, u column-major per column ([r + k*dim + col*ld]), b as
+        [k + col*ld]; a tensor already laid out so is passed as it is, anything else is made so once."""
+        if dim != self.dim:
+            raise ValueError(f"DimensionMismatch: AmortizedPlanarLayer of dimension {self.dim} applied to {dim} rows")
+        if batch != self.batch:
+            raise ValueError(f"DimensionMismatch: planar parameters for {self.batch} columns applied to {batch} columns")
+        if dim > self.MAX_DIM.get(like.dtype, 0):
+            raise ValueError(f"AmortizedPlanarLayer: dim {dim} above the {self.MAX_DIM.get(like.dtype, 0)} rows supported in {like.dtype}")
+        nl = self.n_layers
+        outs, lds = [], []
+        for t in (self.w, self.u):
+            t = t.detach().to(device=like.device, dtype=like.dtype)
+            t = t.unsqueeze(1) if t.dim() == 2 else t
+            ok = (t.stride(0) == 1 or dim <= 1) and (t.stride(1) == dim or nl <= 1) and (t.stride(2) >= dim * nl or batch <= 1)
+            if not ok:
+                t = t.permute(2, 1, 0).contiguous().permute(2, 1, 0)
+            outs.append(t)
+            lds.append(int(t.stride(2)) if batch > 1 else dim * nl)
+        t = self.b.detach().to(device=like.device, dtype=like.dtype)
+        t = t.unsqueeze(0) if t.dim() == 1 else t
+        if not ((t.stride(0) == 1 or nl <= 1) and (t.stride(1) >= nl or batch <= 1)):
+            t = t.T.contiguous().T
+        outs.append(t)
+        lds.append(int(t.stride(1)) if batch > 1 else nl)
+        return outs + lds
+
+    def _run(self, x, inv, per_sample, want_ladj):
+        xc, dim, batch, vec = _prep(x)
+        pw, pu, pb, lw, lu, lb = self._col_params(xc, dim, batch)
+        try:
+            return _call_struct("bjx_planar_cols", x, dim, True, per_sample, want_ladj,
+                                (int(inv), _ptr(pw), _ptr(pu), _ptr(pb), lw, lu, lb, self.n_layers), (dim,))
+        except NotImplementedError as e:                # BJX_ERR_UNSUPPORTED: a size limit of the entry, named in its message
+            raise ValueError(str(e)) from None
+
+    def _wlj(self, x, per_sample, want_ladj=True):
+        return self._run(x, False, per_sample, want_ladj)
+
+    def _wlj_inv(self, x, per_sample, want_ladj=True):
+        return self._run(x, True, per_sample, want_ladj)
+
+    def _pullback(self, x, out_bar, ladj_bar, inv, params):
+        """One bjx_planar_cols_vjp launch: -> (x_bar, {"w", "u", "b"} per column with the constructor's shapes, or None).  The
+        inverse has no parameter outputs (`_vjp_params_inverse` composes them)."""
+        xc, dim, batch, vec = _prep(x)
+        gc, gdim, gbatch, _ = _prep(out_bar)
+        if (gdim, gbatch) != (dim, batch) or gc.dtype != xc.dtype:
+            raise ValueError("DimensionMismatch: out_bar must have the shape and dtype of the output")
+        pw, pu, pb, lw, lu, ldb = self._col_params(xc, dim, batch)
+        lb = _ladj_bar(ladj_bar, batch, xc)
+        ctx = context(xc.device)
+        xb = _empty(dim, batch, xc, vec)
+        nl = self.n_layers
+        wb = ub = bb = None
+        if params:
+            wb, ub = (torch.empty((batch, nl, dim), dtype=xc.dtype, device=xc.device).permute(2, 1, 0) for _ in range(2))
+            bb = torch.empty((batch, nl), dtype=xc.dtype, device=xc.device).T
+        rc = L.load().bjx_planar_cols_vjp(ctx.h, _dt(xc), int(inv), _ptr(pw), _ptr(pu), _ptr(pb), lw, lu, ldb, nl, _ptr(xc), _ptr(gc), _ptr(lb),
+                                          _ptr(xb), _ptr(wb), _ptr(ub), _ptr(bb), dim, batch)
+        L.check(ctx.h, rc, "bjx_planar_cols_vjp")
+        if not params:
+            return xb, None
+        if self.w.dim() == 2:
+            wb, ub = wb[:, 0, :], ub[:, 0, :]
+        return xb, {"w": wb, "u": ub, "b": bb[0] if self.b.dim() == 1 else bb}
 
 
 class RadialLayer(Bijector):
@@ -2970,6 +3065,8 @@ def vjp(b, x, out_bar, ladj_bar=None):
         rc = L.load().bjx_planar_vjp(ctx.h, _dt(xc), int(inv), _ptr(w), _ptr(u), _ptr(bb), base.n_layers, _ptr(xc), _ptr(gc), _ptr(lb), _ptr(xb), dim, batch)
         L.check(ctx.h, rc, "bjx_planar_vjp")
         return xb
+    if isinstance(base, AmortizedPlanarLayer):         # per-column parameters: one bjx_planar_cols_vjp launch, either direction
+        return base._pullback(x, out_bar, ladj_bar, inv, False)[0]
     if isinstance(base, Permute):
         # y = A x with A a permutation matrix: x̄ = Aᵀȳ = the inverse permutation of ȳ (bit-exact gather; log-det 0)
         return transform(base if inv else inverse(base), out_bar)
@@ -3145,7 +3242,7 @@ def _vjp_composed(b, x, out_bar, ladj_bar=None):
 
 def _has_own_params(st):
     base = st.orig if isinstance(st, Inverse) else st
-    return isinstance(base, (PlanarLayer, RadialLayer, RationalQuadraticSpline, InvertibleBatchNorm))
+    return isinstance(base, (PlanarLayer, AmortizedPlanarLayer, RadialLayer, RationalQuadraticSpline, InvertibleBatchNorm))
 
 
 def _radial_runs_unfused(b):
@@ -3452,6 +3549,7 @@ def vjp_params(b, x, out_bar, ladj_bar=None):
     shapes of b.w / b.u / b.b (bjx_planar_vjp_params; closed-form derivatives of planar_layer.jl:65-110).
     For a RadialLayer: (x_bar, {"alpha_", "beta", "z_0"}) — see _vjp_params_radial.
     For inverse(PlanarLayer) / inverse(RadialLayer): the same dictionaries through the implicit function theorem — see _vjp_params_inverse.
+    For an AmortizedPlanarLayer or its inverse: (x_bar, {"w", "u", "b"}) PER COLUMN, not summed, with the shapes of its constructor's arguments.
     For a RationalQuadraticSpline or its inverse: (x_bar, {"widths", "heights", "derivatives"[, "raw_widths", ...]}) — see _vjp_params_rqs
     (a per-column spline, 3-D parameters: the per-column cotangents in its own form, see _rqs_cols_pullback).
     For a Coupling or its inverse: (x_bar, grads) with the cotangents of θ's outputs — {"scale", "shift"} per column (affine law),
@@ -3467,8 +3565,10 @@ def vjp_params(b, x, out_bar, ladj_bar=None):
     if isinstance(b, Coupling) or (isinstance(b, Inverse) and isinstance(b.orig, Coupling)):
         inv = isinstance(b, Inverse)
         return (b.orig if inv else b)._vjp(x, out_bar, ladj_bar, inv, params=True)
-    if isinstance(b, Inverse) and isinstance(b.orig, (PlanarLayer, RadialLayer)):
+    if isinstance(b, Inverse) and isinstance(b.orig, (PlanarLayer, RadialLayer, AmortizedPlanarLayer)):
         return _vjp_params_inverse(b, x, out_bar, ladj_bar)
+    if isinstance(b, AmortizedPlanarLayer):            # (x_bar, {"w", "u", "b"}) PER COLUMN, with the shapes of the constructor's arguments
+        return b._pullback(x, out_bar, ladj_bar, False, True)
     if isinstance(b, RadialLayer):
         return _vjp_params_radial(b, x, out_bar, ladj_bar)
     if isinstance(b, _RadialRun) or (isinstance(b, Inverse) and isinstance(b.orig, _RadialRun)):
@@ -3963,7 +4063,7 @@ def logpdf(td: TransformedDistribution, y, reference_shape: bool = False):
 
 
 # ------------------------------------------------------------------ log-density of a transformed distribution, value AND gradients
-_PARAM_STAGES = ("PlanarLayer", "_PlanarRun", "RadialLayer", "_RadialRun", "RationalQuadraticSpline", "InvertibleBatchNorm", "Coupling", "Scale", "Shift", "Logit",
+_PARAM_STAGES = ("PlanarLayer", "_PlanarRun", "AmortizedPlanarLayer", "RadialLayer", "_RadialRun", "RationalQuadraticSpline", "InvertibleBatchNorm", "Coupling", "Scale", "Shift", "Logit",
                  "LeakyReLU")
 
 
