@@ -204,6 +204,14 @@ SIGNATURES_PLANAR_COLS = {
     "bjx_planar_cols_vjp": (_i, [_vp, _i, _i, _vp, _vp, _vp, _i64, _i64, _i64, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64]),
 }
 
+# include/bjx_radial_cols.h (a RadialLayer stack with one (alpha_, beta, z_0) per column): p_alpha, p_beta, p_z0, ld_a, ld_b, ld_z, n_layers,
+# then the data as bjx_radial / bjx_radial_vjp; the pullback ends with the per-column alpha_bar, beta_bar, z0_bar (any of them may be NULL)
+BJX_RADIAL_COLS_MAX_LAYERS = 64
+SIGNATURES_RADIAL_COLS = {
+    "bjx_radial_cols": (_i, [_vp, _i, _i, _vp, _vp, _vp, _i64, _i64, _i64, _i, _vp, _vp] + _tail),
+    "bjx_radial_cols_vjp": (_i, [_vp, _i, _i, _vp, _vp, _vp, _i64, _i64, _i64, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64]),
+}
+
 _lib = None
 
 
@@ -220,12 +228,13 @@ def load() -> C.CDLL:
     lib = C.CDLL(LIB_PATH, mode=C.RTLD_GLOBAL)
     missing = [n for n in list(SIGNATURES) + list(SIGNATURES_COLS) + list(SIGNATURES_COUPLING) + list(SIGNATURES_CHAIN_VJP) + list(SIGNATURES_RADIAL_STACK)
                + list(SIGNATURES_RADIAL_STACK_PARAMS) + list(SIGNATURES_RADIAL_STACK_LOGPDF) + list(SIGNATURES_PLANAR_LOGPDF) + list(SIGNATURES_PLANAR_COLS)
-               if not hasattr(lib, n)]
+               + list(SIGNATURES_RADIAL_COLS) if not hasattr(lib, n)]
     if missing:  # an incomplete ABI is a build error, not something to paper over
         raise ImportError(f"{LIB_PATH} does not export {missing}; rebuild it")
     for name, (res, args) in (list(SIGNATURES.items()) + list(SIGNATURES_COLS.items()) + list(SIGNATURES_COUPLING.items())
                               + list(SIGNATURES_CHAIN_VJP.items()) + list(SIGNATURES_RADIAL_STACK.items()) + list(SIGNATURES_RADIAL_STACK_PARAMS.items())
-                              + list(SIGNATURES_RADIAL_STACK_LOGPDF.items()) + list(SIGNATURES_PLANAR_LOGPDF.items()) + list(SIGNATURES_PLANAR_COLS.items())):
+                              + list(SIGNATURES_RADIAL_STACK_LOGPDF.items()) + list(SIGNATURES_PLANAR_LOGPDF.items()) + list(SIGNATURES_PLANAR_COLS.items())
+                              + list(SIGNATURES_RADIAL_COLS.items())):
         fn = getattr(lib, name)
         fn.restype = res
         fn.argtypes = args

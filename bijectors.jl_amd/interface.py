@@ -30,7 +30,7 @@ from . import _lib as L
 __all__ = [
     "Transform", "Bijector", "Inverse", "ComposedFunction", "Elementwise", "elementwise", "exp", "log", "identity",
     "Shift", "Scale", "Logit", "LeakyReLU", "TruncatedBijector", "SignFlip", "OrderedBijector", "SimplexBijector",
-    "VecCholeskyBijector", "VecCorrBijector", "CorrBijector", "PDBijector", "PDVecBijector", "Permute", "PlanarLayer", "AmortizedPlanarLayer", "RadialLayer", "InvertibleBatchNorm", "RationalQuadraticSpline",
+    "VecCholeskyBijector", "VecCorrBijector", "CorrBijector", "PDBijector", "PDVecBijector", "Permute", "PlanarLayer", "AmortizedPlanarLayer", "RadialLayer", "AmortizedRadialLayer", "InvertibleBatchNorm", "RationalQuadraticSpline",
     "PartitionMask", "Coupling", "Stacked", "NamedStacked", "Columnwise", "columnwise", "vjp", "istraining", "training", "transform", "inverse", "logabsdetjac", "with_logabsdet_jacobian",
     "with_logabsdet_jacobian_", "transform_", "output_size", "isinvertible", "isclosedform", "colmajor", "context", "_fast_plans",
     "PlanarResult", "vjp_params", "row_moments", "MvNormal", "TorchBase", "TransformedDistribution", "transformed", "logpdf", "logpdf_vjp_params", "rand",
@@ -1741,6 +1741,103 @@ class AmortizedPlanarLayer(Bijector):
         return xb, {"w": wb, "u": ub, "b": bb[0] if self.b.dim() == 1 else bb}
 
 
+class AmortizedRadialLayer(Bijector):
+    """A stack of radial layers (radial_layer.jl:11-133) with one parameter set per COLUMN of the batch — the amortised flow of
+    Rezende & Mohamed (2015), where an encoder emits (α_, β, z₀) for every sample (include/bjx_radial_cols.h).
+
+    `z_0`: (dim, batch) for one layer or (dim, n_layers, batch); `alpha_`, `beta` (the raw scalars behind the softplus): (batch,) or
+    (n_layers, batch).  Layers apply in the order 0 … n_layers−1.  Tensors already laid out column-major per column — a
+    `permute(2, 1, 0)` view of a (batch, n_layers, dim) network output, or a slice of one head [dim·L + 2L, batch] — are passed
+    with their column stride and no copy.  It is NOT a RadialLayer: the composition planner and the fused runs leave it alone;
+    `vjp_params` of the layer and of its inverse (one launch each: the inverse is closed form) return the cotangents of alpha_,
+    beta, z_0 per column, with the shapes given here.  At most 64 layers; dim <= 1 024 in Float32 and 512 in Float64
+    (ValueError otherwise)."""
+
+    MAX_DIM = {torch.float32: 1024, torch.float64: 512}
+
+    def __init__(self, alpha_, beta, z_0):
+        self.alpha_, self.beta, self.z_0 = torch.as_tensor(alpha_), torch.as_tensor(beta), torch.as_tensor(z_0)
+        if self.z_0.dim() not in (2, 3):
+            raise ValueError("DimensionMismatch: expected z_0 of shape (dim, batch) or (dim, n_layers, batch)")
+        self.n_layers = 1 if self.z_0.dim() == 2 else int(self.z_0.shape[1])
+        self.dim, self.batch = int(self.z_0.shape[0]), int(self.z_0.shape[-1])
+        if not 1 <= self.n_layers <= L.BJX_RADIAL_COLS_MAX_LAYERS:
+            raise ValueError(f"AmortizedRadialLayer: {self.n_layers} layers (1 ... {L.BJX_RADIAL_COLS_MAX_LAYERS} supported)")
+        for name, t in (("alpha_", self.alpha_), ("beta", self.beta)):
+            if tuple(t.shape) != (self.n_layers, self.batch) and not (self.n_layers == 1 and tuple(t.shape) == (self.batch,)):
+                raise ValueError(f"DimensionMismatch: expected {name} of shape ({self.n_layers}, {self.batch})" + (f" or ({self.batch},)" if self.n_layers == 1 else ""))
+
+    def _key(self):
+        return (_keyify(self.alpha_), _keyify(self.beta), _keyify(self.z_0))
+
+    def _col_params(self, like, dim, batch):
+        """-> (p_alpha, p_beta, p_z0, ld_a, ld_b, ld_z) for bjx_radial_cols: z_0 column-major per column ([r + k*dim + col*ld]), the
+        scalars as [k + col*ld]; a tensor already laid out so is passed as it is, anything else is made so once (the rule of
+        AmortizedPlanarLayer._col_params)."""
+        if dim != self.dim:
+            raise ValueError(f"DimensionMismatch: AmortizedRadialLayer of dimension {self.dim} applied to {dim} rows")
+        if batch != self.batch:
+            raise ValueError(f"DimensionMismatch: radial parameters for {self.batch} columns applied to {batch} columns")
+        if dim > self.MAX_DIM.get(like.dtype, 0):
+            raise ValueError(f"AmortizedRadialLayer: dim {dim} above the {self.MAX_DIM.get(like.dtype, 0)} rows supported in {like.dtype}")
+        nl = self.n_layers
+        outs, lds = [], []
+        for t in (self.alpha_, self.beta):
+            t = t.detach().to(device=like.device, dtype=like.dtype)
+            t = t.unsqueeze(0) if t.dim() == 1 else t
+            if not ((t.stride(0) == 1 or nl <= 1) and (t.stride(1) >= nl or batch <= 1)):
+                t = t.T.contiguous().T
+            outs.append(t)
+            lds.append(int(t.stride(1)) if batch > 1 else nl)
+        t = self.z_0.detach().to(device=like.device, dtype=like.dtype)
+        t = t.unsqueeze(1) if t.dim() == 2 else t
+        ok = (t.stride(0) == 1 or dim <= 1) and (t.stride(1) == dim or nl <= 1) and (t.stride(2) >= dim * nl or batch <= 1)
+        if not ok:
+            t = t.permute(2, 1, 0).contiguous().permute(2, 1, 0)
+        outs.append(t)
+        lds.append(int(t.stride(2)) if batch > 1 else dim * nl)
+        return outs + lds
+
+    def _run(self, x, inv, per_sample, want_ladj):
+        xc, dim, batch, vec = _prep(x)
+        pa, pb, pz, la, lb, lz = self._col_params(xc, dim, batch)
+        try:
+            return _call_struct("bjx_radial_cols", x, dim, True, per_sample, want_ladj,
+                                (int(inv), _ptr(pa), _ptr(pb), _ptr(pz), la, lb, lz, self.n_layers), (dim,))
+        except NotImplementedError as e:                # BJX_ERR_UNSUPPORTED: a size limit of the entry, named in its message
+            raise ValueError(str(e)) from None
+
+    def _wlj(self, x, per_sample, want_ladj=True):
+        return self._run(x, False, per_sample, want_ladj)
+
+    def _wlj_inv(self, x, per_sample, want_ladj=True):
+        return self._run(x, True, per_sample, want_ladj)
+
+    def _pullback(self, x, out_bar, ladj_bar, inv, params):
+        """One bjx_radial_cols_vjp launch, either direction: -> (x_bar, {"alpha_", "beta", "z_0"} per column with the constructor's
+        shapes, or None)."""
+        xc, dim, batch, vec = _prep(x)
+        gc, gdim, gbatch, _ = _prep(out_bar)
+        if (gdim, gbatch) != (dim, batch) or gc.dtype != xc.dtype:
+            raise ValueError("DimensionMismatch: out_bar must have the shape and dtype of the output")
+        pa, pb, pz, la, ldb, lz = self._col_params(xc, dim, batch)
+        lb = _ladj_bar(ladj_bar, batch, xc)
+        ctx = context(xc.device)
+        xb = _empty(dim, batch, xc, vec)
+        nl = self.n_layers
+        ab = bb = zb = None
+        if params:
+            ab, bb = (torch.empty((batch, nl), dtype=xc.dtype, device=xc.device).T for _ in range(2))
+            zb = torch.empty((batch, nl, dim), dtype=xc.dtype, device=xc.device).permute(2, 1, 0)
+        rc = L.load().bjx_radial_cols_vjp(ctx.h, _dt(xc), int(inv), _ptr(pa), _ptr(pb), _ptr(pz), la, ldb, lz, nl, _ptr(xc), _ptr(gc), _ptr(lb),
+                                          _ptr(xb), _ptr(ab), _ptr(bb), _ptr(zb), dim, batch)
+        L.check(ctx.h, rc, "bjx_radial_cols_vjp")
+        if not params:
+            return xb, None
+        return xb, {"alpha_": ab[0] if self.alpha_.dim() == 1 else ab, "beta": bb[0] if self.beta.dim() == 1 else bb,
+                    "z_0": zb[:, 0, :] if self.z_0.dim() == 2 else zb}
+
+
 class RadialLayer(Bijector):
     """radial_layer.jl:11-133"""
 
@@ -3065,7 +3162,7 @@ def vjp(b, x, out_bar, ladj_bar=None):
         rc = L.load().bjx_planar_vjp(ctx.h, _dt(xc), int(inv), _ptr(w), _ptr(u), _ptr(bb), base.n_layers, _ptr(xc), _ptr(gc), _ptr(lb), _ptr(xb), dim, batch)
         L.check(ctx.h, rc, "bjx_planar_vjp")
         return xb
-    if isinstance(base, AmortizedPlanarLayer):         # per-column parameters: one bjx_planar_cols_vjp launch, either direction
+    if isinstance(base, (AmortizedPlanarLayer, AmortizedRadialLayer)):     # per-column parameters: one bjx_planar_cols_vjp / bjx_radial_cols_vjp launch, either direction
         return base._pullback(x, out_bar, ladj_bar, inv, False)[0]
     if isinstance(base, Permute):
         # y = A x with A a permutation matrix: x̄ = Aᵀȳ = the inverse permutation of ȳ (bit-exact gather; log-det 0)
@@ -3242,7 +3339,7 @@ def _vjp_composed(b, x, out_bar, ladj_bar=None):
 
 def _has_own_params(st):
     base = st.orig if isinstance(st, Inverse) else st
-    return isinstance(base, (PlanarLayer, AmortizedPlanarLayer, RadialLayer, RationalQuadraticSpline, InvertibleBatchNorm))
+    return isinstance(base, (PlanarLayer, AmortizedPlanarLayer, RadialLayer, AmortizedRadialLayer, RationalQuadraticSpline, InvertibleBatchNorm))
 
 
 def _radial_runs_unfused(b):
@@ -3550,6 +3647,7 @@ def vjp_params(b, x, out_bar, ladj_bar=None):
     For a RadialLayer: (x_bar, {"alpha_", "beta", "z_0"}) — see _vjp_params_radial.
     For inverse(PlanarLayer) / inverse(RadialLayer): the same dictionaries through the implicit function theorem — see _vjp_params_inverse.
     For an AmortizedPlanarLayer or its inverse: (x_bar, {"w", "u", "b"}) PER COLUMN, not summed, with the shapes of its constructor's arguments.
+    For an AmortizedRadialLayer or its inverse: (x_bar, {"alpha_", "beta", "z_0"}) PER COLUMN, not summed, one launch in either direction.
     For a RationalQuadraticSpline or its inverse: (x_bar, {"widths", "heights", "derivatives"[, "raw_widths", ...]}) — see _vjp_params_rqs
     (a per-column spline, 3-D parameters: the per-column cotangents in its own form, see _rqs_cols_pullback).
     For a Coupling or its inverse: (x_bar, grads) with the cotangents of θ's outputs — {"scale", "shift"} per column (affine law),
@@ -3565,6 +3663,9 @@ def vjp_params(b, x, out_bar, ladj_bar=None):
     if isinstance(b, Coupling) or (isinstance(b, Inverse) and isinstance(b.orig, Coupling)):
         inv = isinstance(b, Inverse)
         return (b.orig if inv else b)._vjp(x, out_bar, ladj_bar, inv, params=True)
+    if isinstance(b, AmortizedRadialLayer) or (isinstance(b, Inverse) and isinstance(b.orig, AmortizedRadialLayer)):
+        inv = isinstance(b, Inverse)                    # (x_bar, {"alpha_", "beta", "z_0"}) PER COLUMN: one bjx_radial_cols_vjp launch in either direction
+        return (b.orig if inv else b)._pullback(x, out_bar, ladj_bar, inv, True)
     if isinstance(b, Inverse) and isinstance(b.orig, (PlanarLayer, RadialLayer, AmortizedPlanarLayer)):
         return _vjp_params_inverse(b, x, out_bar, ladj_bar)
     if isinstance(b, AmortizedPlanarLayer):            # (x_bar, {"w", "u", "b"}) PER COLUMN, with the shapes of the constructor's arguments
@@ -4063,7 +4164,7 @@ def logpdf(td: TransformedDistribution, y, reference_shape: bool = False):
 
 
 # ------------------------------------------------------------------ log-density of a transformed distribution, value AND gradients
-_PARAM_STAGES = ("PlanarLayer", "_PlanarRun", "AmortizedPlanarLayer", "RadialLayer", "_RadialRun", "RationalQuadraticSpline", "InvertibleBatchNorm", "Coupling", "Scale", "Shift", "Logit",
+_PARAM_STAGES = ("PlanarLayer", "_PlanarRun", "AmortizedPlanarLayer", "RadialLayer", "AmortizedRadialLayer", "_RadialRun", "RationalQuadraticSpline", "InvertibleBatchNorm", "Coupling", "Scale", "Shift", "Logit",
                  "LeakyReLU")
 
 
