@@ -212,6 +212,15 @@ SIGNATURES_RADIAL_COLS = {
     "bjx_radial_cols_vjp": (_i, [_vp, _i, _i, _vp, _vp, _vp, _i64, _i64, _i64, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64]),
 }
 
+# include/bjx_householder_cols.h (Householder reflections with one vector set per column, an optional diagonal head and shift): p_v, p_s,
+# p_m (the last two may be NULL), ld_v, ld_s, ld_m, n_layers, then the data as bjx_radial_cols; the pullback ends with the per-column v_bar,
+# s_bar, m_bar (any of them may be NULL)
+BJX_HOUSEHOLDER_COLS_MAX_LAYERS = 64
+SIGNATURES_HOUSEHOLDER_COLS = {
+    "bjx_householder_cols": (_i, [_vp, _i, _i, _vp, _vp, _vp, _i64, _i64, _i64, _i, _vp, _vp] + _tail),
+    "bjx_householder_cols_vjp": (_i, [_vp, _i, _i, _vp, _vp, _vp, _i64, _i64, _i64, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64]),
+}
+
 _lib = None
 
 
@@ -228,13 +237,13 @@ def load() -> C.CDLL:
     lib = C.CDLL(LIB_PATH, mode=C.RTLD_GLOBAL)
     missing = [n for n in list(SIGNATURES) + list(SIGNATURES_COLS) + list(SIGNATURES_COUPLING) + list(SIGNATURES_CHAIN_VJP) + list(SIGNATURES_RADIAL_STACK)
                + list(SIGNATURES_RADIAL_STACK_PARAMS) + list(SIGNATURES_RADIAL_STACK_LOGPDF) + list(SIGNATURES_PLANAR_LOGPDF) + list(SIGNATURES_PLANAR_COLS)
-               + list(SIGNATURES_RADIAL_COLS) if not hasattr(lib, n)]
+               + list(SIGNATURES_RADIAL_COLS) + list(SIGNATURES_HOUSEHOLDER_COLS) if not hasattr(lib, n)]
     if missing:  # an incomplete ABI is a build error, not something to paper over
         raise ImportError(f"{LIB_PATH} does not export {missing}; rebuild it")
     for name, (res, args) in (list(SIGNATURES.items()) + list(SIGNATURES_COLS.items()) + list(SIGNATURES_COUPLING.items())
                               + list(SIGNATURES_CHAIN_VJP.items()) + list(SIGNATURES_RADIAL_STACK.items()) + list(SIGNATURES_RADIAL_STACK_PARAMS.items())
                               + list(SIGNATURES_RADIAL_STACK_LOGPDF.items()) + list(SIGNATURES_PLANAR_LOGPDF.items()) + list(SIGNATURES_PLANAR_COLS.items())
-                              + list(SIGNATURES_RADIAL_COLS.items())):
+                              + list(SIGNATURES_RADIAL_COLS.items()) + list(SIGNATURES_HOUSEHOLDER_COLS.items())):
         fn = getattr(lib, name)
         fn.restype = res
         fn.argtypes = args

@@ -30,7 +30,7 @@ from . import _lib as L
 __all__ = [
     "Transform", "Bijector", "Inverse", "ComposedFunction", "Elementwise", "elementwise", "exp", "log", "identity",
     "Shift", "Scale", "Logit", "LeakyReLU", "TruncatedBijector", "SignFlip", "OrderedBijector", "SimplexBijector",
-    "VecCholeskyBijector", "VecCorrBijector", "CorrBijector", "PDBijector", "PDVecBijector", "Permute", "PlanarLayer", "AmortizedPlanarLayer", "RadialLayer", "AmortizedRadialLayer", "InvertibleBatchNorm", "RationalQuadraticSpline",
+    "VecCholeskyBijector", "VecCorrBijector", "CorrBijector", "PDBijector", "PDVecBijector", "Permute", "PlanarLayer", "AmortizedPlanarLayer", "RadialLayer", "AmortizedRadialLayer", "AmortizedHouseholderFlow", "InvertibleBatchNorm", "RationalQuadraticSpline",
     "PartitionMask", "Coupling", "Stacked", "NamedStacked", "Columnwise", "columnwise", "vjp", "istraining", "training", "transform", "inverse", "logabsdetjac", "with_logabsdet_jacobian",
     "with_logabsdet_jacobian_", "transform_", "output_size", "isinvertible", "isclosedform", "colmajor", "context", "_fast_plans",
     "PlanarResult", "vjp_params", "row_moments", "MvNormal", "TorchBase", "TransformedDistribution", "transformed", "logpdf", "logpdf_vjp_params", "rand",
@@ -1838,6 +1838,116 @@ class AmortizedRadialLayer(Bijector):
                     "z_0": zb[:, 0, :] if self.z_0.dim() == 2 else zb}
 
 
+class AmortizedHouseholderFlow(Bijector):
+    """A product of Householder reflections with one vector set per COLUMN of the batch, behind an optional per-column diagonal
+    scale and in front of an optional per-column shift — the amortised Householder flow of Tomczak & Welling (2016), where an encoder
+    emits (v, log_scale, shift) for every sample (include/bjx_householder_cols.h):
+
+        u = exp(log_scale) ⊙ x;   z_{k+1} = z_k − 2 (v_kᵀz_k / v_kᵀv_k) v_k;   y = z_L + shift;   logabsdetjac = Σ log_scale
+
+    so that a standard-normal x gives y ~ N(shift, U diag(exp(2·log_scale)) Uᵀ) with U = H_{L−1}⋯H_0.  With one layer's v == 0
+    exactly that layer is the identity (and its cotangent 0).
+
+    `v`: (dim, batch) for one layer or (dim, n_layers, batch); `log_scale`, `shift`: (dim, batch) or None (absent).  Layers apply
+    in the order 0 … n_layers−1.  Tensors already laid out column-major per column — a `permute(2, 1, 0)` view of a
+    (batch, n_layers, dim) network output, or slices of one head [dim·L + 2·dim, batch] — are passed with their column stride and no
+    copy.  `vjp_params` of the flow and of its inverse (one launch each: a reflection is its own inverse) return the cotangents of
+    v, log_scale, shift per column, with the shapes given here; the key of an absent parameter is omitted.  At most 64 layers;
+    dim <= 1 024 in Float32 and 512 in Float64 (ValueError otherwise)."""
+
+    MAX_DIM = {torch.float32: 1024, torch.float64: 512}
+
+    def __init__(self, v, log_scale=None, shift=None):
+        self.v = torch.as_tensor(v)
+        self.log_scale = None if log_scale is None else torch.as_tensor(log_scale)
+        self.shift = None if shift is None else torch.as_tensor(shift)
+        if self.v.dim() not in (2, 3):
+            raise ValueError("DimensionMismatch: expected v of shape (dim, batch) or (dim, n_layers, batch)")
+        self.n_layers = 1 if self.v.dim() == 2 else int(self.v.shape[1])
+        self.dim, self.batch = int(self.v.shape[0]), int(self.v.shape[-1])
+        if not 1 <= self.n_layers <= L.BJX_HOUSEHOLDER_COLS_MAX_LAYERS:
+            raise ValueError(f"AmortizedHouseholderFlow: {self.n_layers} layers (1 ... {L.BJX_HOUSEHOLDER_COLS_MAX_LAYERS} supported)")
+        for name, t in (("log_scale", self.log_scale), ("shift", self.shift)):
+            if t is not None and tuple(t.shape) != (self.dim, self.batch):
+                raise ValueError(f"DimensionMismatch: expected {name} of shape ({self.dim}, {self.batch})")
+
+    def _key(self):
+        return (_keyify(self.v), None if self.log_scale is None else _keyify(self.log_scale), None if self.shift is None else _keyify(self.shift))
+
+    def _col_params(self, like, dim, batch):
+        """-> (p_v, p_s, p_m, ld_v, ld_s, ld_m) for bjx_householder_cols: v column-major per column ([r + k*dim + col*ld]), log_scale and
+        shift as [r + col*ld] (None and ld 0 when absent); a tensor already laid out so is passed as it is, anything else is made so
+        once (the rule of AmortizedRadialLayer._col_params)."""
+        if dim != self.dim:
+            raise ValueError(f"DimensionMismatch: AmortizedHouseholderFlow of dimension {self.dim} applied to {dim} rows")
+        if batch != self.batch:
+            raise ValueError(f"DimensionMismatch: Householder parameters for {self.batch} columns applied to {batch} columns")
+        if dim > self.MAX_DIM.get(like.dtype, 0):
+            raise ValueError(f"AmortizedHouseholderFlow: dim {dim} above the {self.MAX_DIM.get(like.dtype, 0)} rows supported in {like.dtype}")
+        nl = self.n_layers
+        t = self.v.detach().to(device=like.device, dtype=like.dtype)
+        t = t.unsqueeze(1) if t.dim() == 2 else t
+        ok = (t.stride(0) == 1 or dim <= 1) and (t.stride(1) == dim or nl <= 1) and (t.stride(2) >= dim * nl or batch <= 1)
+        if not ok:
+            t = t.permute(2, 1, 0).contiguous().permute(2, 1, 0)
+        outs, lds = [t], [int(t.stride(2)) if batch > 1 else dim * nl]
+        for t in (self.log_scale, self.shift):
+            if t is None:
+                outs.append(None)
+                lds.append(0)
+                continue
+            t = t.detach().to(device=like.device, dtype=like.dtype)
+            if not ((t.stride(0) == 1 or dim <= 1) and (t.stride(1) >= dim or batch <= 1)):
+                t = t.T.contiguous().T
+            outs.append(t)
+            lds.append(int(t.stride(1)) if batch > 1 else dim)
+        return outs + lds
+
+    def _run(self, x, inv, per_sample, want_ladj):
+        xc, dim, batch, vec = _prep(x)
+        pv, ps, pm, lv, ls, lm = self._col_params(xc, dim, batch)
+        try:
+            return _call_struct("bjx_householder_cols", x, dim, True, per_sample, want_ladj,
+                                (int(inv), _ptr(pv), _ptr(ps), _ptr(pm), lv, ls, lm, self.n_layers), (dim,))
+        except NotImplementedError as e:                # BJX_ERR_UNSUPPORTED: a size limit of the entry, named in its message
+            raise ValueError(str(e)) from None
+
+    def _wlj(self, x, per_sample, want_ladj=True):
+        return self._run(x, False, per_sample, want_ladj)
+
+    def _wlj_inv(self, x, per_sample, want_ladj=True):
+        return self._run(x, True, per_sample, want_ladj)
+
+    def _pullback(self, x, out_bar, ladj_bar, inv, params):
+        """One bjx_householder_cols_vjp launch, either direction: -> (x_bar, {"v", "log_scale", "shift"} per column with the
+        constructor's shapes and without the keys of absent parameters, or None)."""
+        xc, dim, batch, vec = _prep(x)
+        gc, gdim, gbatch, _ = _prep(out_bar)
+        if (gdim, gbatch) != (dim, batch) or gc.dtype != xc.dtype:
+            raise ValueError("DimensionMismatch: out_bar must have the shape and dtype of the output")
+        pv, ps, pm, lv, ls, lm = self._col_params(xc, dim, batch)
+        lb = _ladj_bar(ladj_bar, batch, xc)
+        ctx = context(xc.device)
+        xb = _empty(dim, batch, xc, vec)
+        nl = self.n_layers
+        vb = sb = mb = None
+        if params:
+            vb = torch.empty((batch, nl, dim), dtype=xc.dtype, device=xc.device).permute(2, 1, 0)
+            sb = None if ps is None else torch.empty((batch, dim), dtype=xc.dtype, device=xc.device).T
+            mb = None if pm is None else torch.empty((batch, dim), dtype=xc.dtype, device=xc.device).T
+        rc = L.load().bjx_householder_cols_vjp(ctx.h, _dt(xc), int(inv), _ptr(pv), _ptr(ps), _ptr(pm), lv, ls, lm, nl, _ptr(xc), _ptr(gc), _ptr(lb),
+                                               _ptr(xb), _ptr(vb), _ptr(sb), _ptr(mb), dim, batch)
+        L.check(ctx.h, rc, "bjx_householder_cols_vjp")
+        if not params:
+            return xb, None
+        grads = {"v": vb[:, 0, :] if self.v.dim() == 2 else vb}
+        if sb is not None:
+            grads["log_scale"] = sb
+        if mb is not None:
+            grads["shift"] = mb
+        return xb, grads
+
+
 class RadialLayer(Bijector):
     """radial_layer.jl:11-133"""
 
@@ -3162,7 +3272,7 @@ def vjp(b, x, out_bar, ladj_bar=None):
         rc = L.load().bjx_planar_vjp(ctx.h, _dt(xc), int(inv), _ptr(w), _ptr(u), _ptr(bb), base.n_layers, _ptr(xc), _ptr(gc), _ptr(lb), _ptr(xb), dim, batch)
         L.check(ctx.h, rc, "bjx_planar_vjp")
         return xb
-    if isinstance(base, (AmortizedPlanarLayer, AmortizedRadialLayer)):     # per-column parameters: one bjx_planar_cols_vjp / bjx_radial_cols_vjp launch, either direction
+    if isinstance(base, (AmortizedPlanarLayer, AmortizedRadialLayer, AmortizedHouseholderFlow)):     # per-column parameters: one bjx_planar_cols_vjp / bjx_radial_cols_vjp / bjx_householder_cols_vjp launch, either direction
         return base._pullback(x, out_bar, ladj_bar, inv, False)[0]
     if isinstance(base, Permute):
         # y = A x with A a permutation matrix: x̄ = Aᵀȳ = the inverse permutation of ȳ (bit-exact gather; log-det 0)
@@ -3339,7 +3449,7 @@ def _vjp_composed(b, x, out_bar, ladj_bar=None):
 
 def _has_own_params(st):
     base = st.orig if isinstance(st, Inverse) else st
-    return isinstance(base, (PlanarLayer, AmortizedPlanarLayer, RadialLayer, AmortizedRadialLayer, RationalQuadraticSpline, InvertibleBatchNorm))
+    return isinstance(base, (PlanarLayer, AmortizedPlanarLayer, RadialLayer, AmortizedRadialLayer, AmortizedHouseholderFlow, RationalQuadraticSpline, InvertibleBatchNorm))
 
 
 def _radial_runs_unfused(b):
@@ -3648,6 +3758,8 @@ def vjp_params(b, x, out_bar, ladj_bar=None):
     For inverse(PlanarLayer) / inverse(RadialLayer): the same dictionaries through the implicit function theorem — see _vjp_params_inverse.
     For an AmortizedPlanarLayer or its inverse: (x_bar, {"w", "u", "b"}) PER COLUMN, not summed, with the shapes of its constructor's arguments.
     For an AmortizedRadialLayer or its inverse: (x_bar, {"alpha_", "beta", "z_0"}) PER COLUMN, not summed, one launch in either direction.
+    For an AmortizedHouseholderFlow or its inverse: (x_bar, {"v", "log_scale", "shift"}) PER COLUMN, not summed, one launch in either direction;
+    the key of an absent parameter is omitted.
     For a RationalQuadraticSpline or its inverse: (x_bar, {"widths", "heights", "derivatives"[, "raw_widths", ...]}) — see _vjp_params_rqs
     (a per-column spline, 3-D parameters: the per-column cotangents in its own form, see _rqs_cols_pullback).
     For a Coupling or its inverse: (x_bar, grads) with the cotangents of θ's outputs — {"scale", "shift"} per column (affine law),
@@ -3663,8 +3775,8 @@ def vjp_params(b, x, out_bar, ladj_bar=None):
     if isinstance(b, Coupling) or (isinstance(b, Inverse) and isinstance(b.orig, Coupling)):
         inv = isinstance(b, Inverse)
         return (b.orig if inv else b)._vjp(x, out_bar, ladj_bar, inv, params=True)
-    if isinstance(b, AmortizedRadialLayer) or (isinstance(b, Inverse) and isinstance(b.orig, AmortizedRadialLayer)):
-        inv = isinstance(b, Inverse)                    # (x_bar, {"alpha_", "beta", "z_0"}) PER COLUMN: one bjx_radial_cols_vjp launch in either direction
+    if isinstance(b, (AmortizedRadialLayer, AmortizedHouseholderFlow)) or (isinstance(b, Inverse) and isinstance(b.orig, (AmortizedRadialLayer, AmortizedHouseholderFlow))):
+        inv = isinstance(b, Inverse)                    # (x_bar, {"alpha_", "beta", "z_0"} / {"v", "log_scale", "shift"}) PER COLUMN: one launch in either direction
         return (b.orig if inv else b)._pullback(x, out_bar, ladj_bar, inv, True)
     if isinstance(b, Inverse) and isinstance(b.orig, (PlanarLayer, RadialLayer, AmortizedPlanarLayer)):
         return _vjp_params_inverse(b, x, out_bar, ladj_bar)
@@ -4164,7 +4276,7 @@ def logpdf(td: TransformedDistribution, y, reference_shape: bool = False):
 
 
 # ------------------------------------------------------------------ log-density of a transformed distribution, value AND gradients
-_PARAM_STAGES = ("PlanarLayer", "_PlanarRun", "AmortizedPlanarLayer", "RadialLayer", "AmortizedRadialLayer", "_RadialRun", "RationalQuadraticSpline", "InvertibleBatchNorm", "Coupling", "Scale", "Shift", "Logit",
+_PARAM_STAGES = ("PlanarLayer", "_PlanarRun", "AmortizedPlanarLayer", "RadialLayer", "AmortizedRadialLayer", "AmortizedHouseholderFlow", "_RadialRun", "RationalQuadraticSpline", "InvertibleBatchNorm", "Coupling", "Scale", "Shift", "Logit",
                  "LeakyReLU")
 
 
