@@ -221,6 +221,21 @@ SIGNATURES_HOUSEHOLDER_COLS = {
     "bjx_householder_cols_vjp": (_i, [_vp, _i, _i, _vp, _vp, _vp, _i64, _i64, _i64, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64]),
 }
 
+# include/bjx_householder.h (Householder reflections with ONE vector set shared by every column): inverse, v T[dim, n_layers], n_layers,
+# then the data as bjx_radial; the parameter pullback takes in, out_bar, ladj_bar (ignored), in_bar (may be NULL), v_bar T[dim, n_layers]
+BJX_HOUSEHOLDER_MAX_LAYERS = 64
+BJX_HOUSEHOLDER_LDS_BUDGET = 65536
+SIGNATURES_HOUSEHOLDER = {
+    "bjx_householder": (_i, [_vp, _i, _i, _vp, _i, _vp, _vp] + _tail),
+    "bjx_householder_vjp_params": (_i, [_vp, _i, _i, _vp, _i, _vp, _vp, _vp, _vp, _vp, _i64, _i64]),
+}
+
+
+def householder_lds_bytes(dim: int, n_layers: int) -> int:
+    """BJX_HOUSEHOLDER_LDS_BYTES of include/bjx_householder.h: four Float64 tables [n_layers][dim + 1] and n_layers values t_k."""
+    return 8 * n_layers * (4 * (dim + 1) + 1)
+
+
 _lib = None
 
 
@@ -237,13 +252,13 @@ def load() -> C.CDLL:
     lib = C.CDLL(LIB_PATH, mode=C.RTLD_GLOBAL)
     missing = [n for n in list(SIGNATURES) + list(SIGNATURES_COLS) + list(SIGNATURES_COUPLING) + list(SIGNATURES_CHAIN_VJP) + list(SIGNATURES_RADIAL_STACK)
                + list(SIGNATURES_RADIAL_STACK_PARAMS) + list(SIGNATURES_RADIAL_STACK_LOGPDF) + list(SIGNATURES_PLANAR_LOGPDF) + list(SIGNATURES_PLANAR_COLS)
-               + list(SIGNATURES_RADIAL_COLS) + list(SIGNATURES_HOUSEHOLDER_COLS) if not hasattr(lib, n)]
+               + list(SIGNATURES_RADIAL_COLS) + list(SIGNATURES_HOUSEHOLDER_COLS) + list(SIGNATURES_HOUSEHOLDER) if not hasattr(lib, n)]
     if missing:  # an incomplete ABI is a build error, not something to paper over
         raise ImportError(f"{LIB_PATH} does not export {missing}; rebuild it")
     for name, (res, args) in (list(SIGNATURES.items()) + list(SIGNATURES_COLS.items()) + list(SIGNATURES_COUPLING.items())
                               + list(SIGNATURES_CHAIN_VJP.items()) + list(SIGNATURES_RADIAL_STACK.items()) + list(SIGNATURES_RADIAL_STACK_PARAMS.items())
                               + list(SIGNATURES_RADIAL_STACK_LOGPDF.items()) + list(SIGNATURES_PLANAR_LOGPDF.items()) + list(SIGNATURES_PLANAR_COLS.items())
-                              + list(SIGNATURES_RADIAL_COLS.items()) + list(SIGNATURES_HOUSEHOLDER_COLS.items())):
+                              + list(SIGNATURES_RADIAL_COLS.items()) + list(SIGNATURES_HOUSEHOLDER_COLS.items()) + list(SIGNATURES_HOUSEHOLDER.items())):
         fn = getattr(lib, name)
         fn.restype = res
         fn.argtypes = args

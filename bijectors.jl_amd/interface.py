@@ -30,7 +30,7 @@ from . import _lib as L
 __all__ = [
     "Transform", "Bijector", "Inverse", "ComposedFunction", "Elementwise", "elementwise", "exp", "log", "identity",
     "Shift", "Scale", "Logit", "LeakyReLU", "TruncatedBijector", "SignFlip", "OrderedBijector", "SimplexBijector",
-    "VecCholeskyBijector", "VecCorrBijector", "CorrBijector", "PDBijector", "PDVecBijector", "Permute", "PlanarLayer", "AmortizedPlanarLayer", "RadialLayer", "AmortizedRadialLayer", "AmortizedHouseholderFlow", "InvertibleBatchNorm", "RationalQuadraticSpline",
+    "VecCholeskyBijector", "VecCorrBijector", "CorrBijector", "PDBijector", "PDVecBijector", "Permute", "PlanarLayer", "AmortizedPlanarLayer", "RadialLayer", "AmortizedRadialLayer", "AmortizedHouseholderFlow", "HouseholderLayer", "InvertibleBatchNorm", "RationalQuadraticSpline",
     "PartitionMask", "Coupling", "Stacked", "NamedStacked", "Columnwise", "columnwise", "vjp", "istraining", "training", "transform", "inverse", "logabsdetjac", "with_logabsdet_jacobian",
     "with_logabsdet_jacobian_", "transform_", "output_size", "isinvertible", "isclosedform", "colmajor", "context", "_fast_plans",
     "PlanarResult", "vjp_params", "row_moments", "MvNormal", "TorchBase", "TransformedDistribution", "transformed", "logpdf", "logpdf_vjp_params", "rand",
@@ -1948,6 +1948,106 @@ class AmortizedHouseholderFlow(Bijector):
         return xb, grads
 
 
+_HH_LDS_REFUSED: set = set()      # (dtype, dim, n_layers) whose Float64 tables bjx_householder_vjp_params refused: they take the chunked fallback
+_HH_FALLBACK_ELEMS = 1 << 25      # elements of the expanded v (and of the per-column v̄) one chunk of the fallback holds
+
+
+class HouseholderLayer(Bijector):
+    """A product of Householder reflections with ONE vector set shared by every column (include/bjx_householder.h) — the trainable
+    orthogonal mixing layer between coupling layers; the shared half of the pair whose per-column half is AmortizedHouseholderFlow:
+
+        z_{k+1} = z_k − 2 (v_kᵀz_k / v_kᵀv_k) v_k,   y = z_L,   logabsdetjac = 0 exactly
+
+    `v`: (dim,) for one layer or (dim, n_layers); layers apply in the order 0 … n_layers−1.  The inverse is closed form (the same
+    reflections in reverse order).  A layer with v_k == 0 exactly is the identity and its cotangent is 0.  `vjp` is the other
+    direction's map applied to `out_bar`; `vjp_params` of the layer and of its inverse return (x_bar, {"v": v_bar}) with the
+    constructor's shape, SUMMED over the batch: one streaming pass and one or two folds (bjx_householder_vjp_params).  Where that
+    entry refuses because its Float64 tables exceed the LDS budget (`_lib.householder_lds_bytes(dim, n_layers)` above 64 KiB) the
+    parameters are expanded over chunks of columns, the chunks go through bjx_householder_cols_vjp and their per-column v̄ are summed
+    in Float64 in a fixed order; the expanded v and the per-column v̄ of a chunk hold at most 2²⁵ elements each (128 MiB in Float32,
+    256 MiB in Float64).  At most 64 layers; dim <= 1 024 in Float32 and 512 in Float64 (ValueError otherwise)."""
+
+    MAX_DIM = {torch.float32: 1024, torch.float64: 512}
+
+    def __init__(self, v):
+        self.v = torch.as_tensor(v)
+        if self.v.dim() not in (1, 2):
+            raise ValueError("DimensionMismatch: expected v of shape (dim,) or (dim, n_layers)")
+        self.dim = int(self.v.shape[0])
+        self.n_layers = 1 if self.v.dim() == 1 else int(self.v.shape[1])
+        if self.dim < 1:
+            raise ValueError("DimensionMismatch: expected v with at least one row")
+        if not 1 <= self.n_layers <= L.BJX_HOUSEHOLDER_MAX_LAYERS:
+            raise ValueError(f"HouseholderLayer: {self.n_layers} layers (1 ... {L.BJX_HOUSEHOLDER_MAX_LAYERS} supported)")
+
+    def _key(self):
+        return (_keyify(self.v),)
+
+    def _table(self, like, dim):
+        """-> v on the device as dense T[dim, n_layers], layer k at v + k*dim."""
+        if dim != self.dim:
+            raise ValueError(f"DimensionMismatch: HouseholderLayer of dimension {self.dim} applied to {dim} rows")
+        if dim > self.MAX_DIM.get(like.dtype, 0):
+            raise ValueError(f"HouseholderLayer: dim {dim} above the {self.MAX_DIM.get(like.dtype, 0)} rows supported in {like.dtype}")
+        return colmajor(_param(self.v, like))
+
+    def _run(self, x, inv, per_sample, want_ladj):
+        xc, dim, batch, vec = _prep(x)
+        v = self._table(xc, dim)
+        return _call_struct("bjx_householder", x, dim, True, per_sample, want_ladj, (int(inv), _ptr(v), self.n_layers), (dim,))
+
+    def _wlj(self, x, per_sample, want_ladj=True):
+        return self._run(x, False, per_sample, want_ladj)
+
+    def _wlj_inv(self, x, per_sample, want_ladj=True):
+        return self._run(x, True, per_sample, want_ladj)
+
+    def _vjp_params(self, x, out_bar, ladj_bar, inv):
+        """-> (x_bar, {"v": v_bar summed over the batch, the constructor's shape}); `ladj_bar` contributes nothing (the log-det is 0)."""
+        xc, dim, batch, vec = _prep(x)
+        gc, gdim, gbatch, _ = _prep(out_bar)
+        if (gdim, gbatch) != (dim, batch) or gc.dtype != xc.dtype:
+            raise ValueError("DimensionMismatch: out_bar must have the shape and dtype of the output")
+        v = self._table(xc, dim)
+        _ladj_bar(ladj_bar, batch, xc)                  # shape errors only
+        nl = self.n_layers
+        ctx = context(xc.device)
+        xb = _empty(dim, batch, xc, vec)
+        key = (xc.dtype, dim, nl)
+        vb = None
+        if key not in _HH_LDS_REFUSED:
+            vb = torch.empty((nl, dim), dtype=xc.dtype, device=xc.device).T
+            rc = L.load().bjx_householder_vjp_params(ctx.h, _dt(xc), int(inv), _ptr(v), nl, _ptr(xc), _ptr(gc), None, _ptr(xb), _ptr(vb), dim, batch)
+            if rc == L.ERR_UNSUPPORTED:                 # the sizes were checked above: only the LDS rule is left
+                _HH_LDS_REFUSED.add(key)
+                vb = None
+            else:
+                L.check(ctx.h, rc, "bjx_householder_vjp_params")
+        if vb is None:
+            vb = self._vjp_params_chunked(ctx, v, xc, gc, xb, inv, dim, batch)
+        return xb, {"v": vb[:, 0] if self.v.dim() == 1 else vb}
+
+    def _vjp_params_chunked(self, ctx, v, xc, gc, xb, inv, dim, batch):
+        """The fallback of `_vjp_params`: chunks of columns with the parameters expanded per column through bjx_householder_cols_vjp,
+        the per-column v̄ summed over each chunk and the chunks added in order, in Float64 (torch's sum over one axis has a fixed
+        order).  Scratch: the expanded v and the per-column v̄ of one chunk, `_HH_FALLBACK_ELEMS` elements each at the most."""
+        nl = self.n_layers
+        chunk = max(1, _HH_FALLBACK_ELEMS // (dim * nl))
+        acc = torch.zeros((nl, dim), dtype=torch.float64, device=xc.device)
+        esz = xc.element_size()
+        rows = v.reshape(dim, nl).T.reshape(1, nl, dim)
+        for lo in range(0, batch, chunk):
+            n = min(chunk, batch - lo)
+            ve = rows.expand(n, nl, dim).contiguous()            # (n, n_layers, dim): column-major per column
+            vbc = torch.empty((n, nl, dim), dtype=xc.dtype, device=xc.device)
+            off = lo * dim * esz
+            rc = L.load().bjx_householder_cols_vjp(ctx.h, _dt(xc), int(inv), _ptr(ve), None, None, dim * nl, 0, 0, nl, C.c_void_p(xc.data_ptr() + off),
+                                                   C.c_void_p(gc.data_ptr() + off), None, C.c_void_p(xb.data_ptr() + off), _ptr(vbc), None, None, dim, n)
+            L.check(ctx.h, rc, "bjx_householder_cols_vjp")
+            acc += vbc.to(torch.float64).sum(dim=0)
+        return acc.to(xc.dtype).T
+
+
 class RadialLayer(Bijector):
     """radial_layer.jl:11-133"""
 
@@ -3274,6 +3374,11 @@ def vjp(b, x, out_bar, ladj_bar=None):
         return xb
     if isinstance(base, (AmortizedPlanarLayer, AmortizedRadialLayer, AmortizedHouseholderFlow)):     # per-column parameters: one bjx_planar_cols_vjp / bjx_radial_cols_vjp / bjx_householder_cols_vjp launch, either direction
         return base._pullback(x, out_bar, ladj_bar, inv, False)[0]
+    if isinstance(base, HouseholderLayer):
+        # y = U x with U orthogonal and symmetric factors: x̄ = Uᵀȳ = the other direction's map of ȳ (log-det 0: ladj_bar adds nothing)
+        if tuple(out_bar.shape) != tuple(x.shape) or out_bar.dtype != x.dtype:
+            raise ValueError("DimensionMismatch: out_bar must have the shape and dtype of the output")
+        return transform(base if inv else inverse(base), out_bar)
     if isinstance(base, Permute):
         # y = A x with A a permutation matrix: x̄ = Aᵀȳ = the inverse permutation of ȳ (bit-exact gather; log-det 0)
         return transform(base if inv else inverse(base), out_bar)
@@ -3449,7 +3554,7 @@ def _vjp_composed(b, x, out_bar, ladj_bar=None):
 
 def _has_own_params(st):
     base = st.orig if isinstance(st, Inverse) else st
-    return isinstance(base, (PlanarLayer, AmortizedPlanarLayer, RadialLayer, AmortizedRadialLayer, AmortizedHouseholderFlow, RationalQuadraticSpline, InvertibleBatchNorm))
+    return isinstance(base, (PlanarLayer, AmortizedPlanarLayer, RadialLayer, AmortizedRadialLayer, AmortizedHouseholderFlow, HouseholderLayer, RationalQuadraticSpline, InvertibleBatchNorm))
 
 
 def _radial_runs_unfused(b):
@@ -3760,6 +3865,7 @@ def vjp_params(b, x, out_bar, ladj_bar=None):
     For an AmortizedRadialLayer or its inverse: (x_bar, {"alpha_", "beta", "z_0"}) PER COLUMN, not summed, one launch in either direction.
     For an AmortizedHouseholderFlow or its inverse: (x_bar, {"v", "log_scale", "shift"}) PER COLUMN, not summed, one launch in either direction;
     the key of an absent parameter is omitted.
+    For a HouseholderLayer or its inverse: (x_bar, {"v"}) summed over the batch, with the constructor's shape (bjx_householder_vjp_params).
     For a RationalQuadraticSpline or its inverse: (x_bar, {"widths", "heights", "derivatives"[, "raw_widths", ...]}) — see _vjp_params_rqs
     (a per-column spline, 3-D parameters: the per-column cotangents in its own form, see _rqs_cols_pullback).
     For a Coupling or its inverse: (x_bar, grads) with the cotangents of θ's outputs — {"scale", "shift"} per column (affine law),
@@ -3778,6 +3884,9 @@ def vjp_params(b, x, out_bar, ladj_bar=None):
     if isinstance(b, (AmortizedRadialLayer, AmortizedHouseholderFlow)) or (isinstance(b, Inverse) and isinstance(b.orig, (AmortizedRadialLayer, AmortizedHouseholderFlow))):
         inv = isinstance(b, Inverse)                    # (x_bar, {"alpha_", "beta", "z_0"} / {"v", "log_scale", "shift"}) PER COLUMN: one launch in either direction
         return (b.orig if inv else b)._pullback(x, out_bar, ladj_bar, inv, True)
+    if isinstance(b, HouseholderLayer) or (isinstance(b, Inverse) and isinstance(b.orig, HouseholderLayer)):
+        inv = isinstance(b, Inverse)                    # (x_bar, {"v"}) summed over the batch: one pass and its folds, either direction
+        return (b.orig if inv else b)._vjp_params(x, out_bar, ladj_bar, inv)
     if isinstance(b, Inverse) and isinstance(b.orig, (PlanarLayer, RadialLayer, AmortizedPlanarLayer)):
         return _vjp_params_inverse(b, x, out_bar, ladj_bar)
     if isinstance(b, AmortizedPlanarLayer):            # (x_bar, {"w", "u", "b"}) PER COLUMN, with the shapes of the constructor's arguments
@@ -4276,7 +4385,7 @@ def logpdf(td: TransformedDistribution, y, reference_shape: bool = False):
 
 
 # ------------------------------------------------------------------ log-density of a transformed distribution, value AND gradients
-_PARAM_STAGES = ("PlanarLayer", "_PlanarRun", "AmortizedPlanarLayer", "RadialLayer", "AmortizedRadialLayer", "AmortizedHouseholderFlow", "_RadialRun", "RationalQuadraticSpline", "InvertibleBatchNorm", "Coupling", "Scale", "Shift", "Logit",
+_PARAM_STAGES = ("PlanarLayer", "_PlanarRun", "AmortizedPlanarLayer", "RadialLayer", "AmortizedRadialLayer", "AmortizedHouseholderFlow", "HouseholderLayer", "_RadialRun", "RationalQuadraticSpline", "InvertibleBatchNorm", "Coupling", "Scale", "Shift", "Logit",
                  "LeakyReLU")
 
 
