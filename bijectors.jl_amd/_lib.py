@@ -230,6 +230,14 @@ SIGNATURES_HOUSEHOLDER = {
     "bjx_householder_vjp_params": (_i, [_vp, _i, _i, _vp, _i, _vp, _vp, _vp, _vp, _vp, _i64, _i64]),
 }
 
+# include/bjx_sylvester_cols.h (one Sylvester layer with (Q, R, R~, b) per column): p_q, p_r, p_rt, p_b, ld_q, ld_r, ld_rt, ld_b, M, then the data
+# as bjx_householder_cols; the pullback ends with the per-column q_bar, r_bar, rt_bar, b_bar (any of them may be NULL)
+BJX_SYLVESTER_COLS_MAX_UNITS = 16
+SIGNATURES_SYLVESTER_COLS = {
+    "bjx_sylvester_cols": (_i, [_vp, _i, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _i, _vp, _vp] + _tail),
+    "bjx_sylvester_cols_vjp": (_i, [_vp, _i, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64]),
+}
+
 
 def householder_lds_bytes(dim: int, n_layers: int) -> int:
     """BJX_HOUSEHOLDER_LDS_BYTES of include/bjx_householder.h: four Float64 tables [n_layers][dim + 1] and n_layers values t_k."""
@@ -252,13 +260,14 @@ def load() -> C.CDLL:
     lib = C.CDLL(LIB_PATH, mode=C.RTLD_GLOBAL)
     missing = [n for n in list(SIGNATURES) + list(SIGNATURES_COLS) + list(SIGNATURES_COUPLING) + list(SIGNATURES_CHAIN_VJP) + list(SIGNATURES_RADIAL_STACK)
                + list(SIGNATURES_RADIAL_STACK_PARAMS) + list(SIGNATURES_RADIAL_STACK_LOGPDF) + list(SIGNATURES_PLANAR_LOGPDF) + list(SIGNATURES_PLANAR_COLS)
-               + list(SIGNATURES_RADIAL_COLS) + list(SIGNATURES_HOUSEHOLDER_COLS) + list(SIGNATURES_HOUSEHOLDER) if not hasattr(lib, n)]
+               + list(SIGNATURES_RADIAL_COLS) + list(SIGNATURES_HOUSEHOLDER_COLS) + list(SIGNATURES_HOUSEHOLDER) + list(SIGNATURES_SYLVESTER_COLS) if not hasattr(lib, n)]
     if missing:  # an incomplete ABI is a build error, not something to paper over
         raise ImportError(f"{LIB_PATH} does not export {missing}; rebuild it")
     for name, (res, args) in (list(SIGNATURES.items()) + list(SIGNATURES_COLS.items()) + list(SIGNATURES_COUPLING.items())
                               + list(SIGNATURES_CHAIN_VJP.items()) + list(SIGNATURES_RADIAL_STACK.items()) + list(SIGNATURES_RADIAL_STACK_PARAMS.items())
                               + list(SIGNATURES_RADIAL_STACK_LOGPDF.items()) + list(SIGNATURES_PLANAR_LOGPDF.items()) + list(SIGNATURES_PLANAR_COLS.items())
-                              + list(SIGNATURES_RADIAL_COLS.items()) + list(SIGNATURES_HOUSEHOLDER_COLS.items()) + list(SIGNATURES_HOUSEHOLDER.items())):
+                              + list(SIGNATURES_RADIAL_COLS.items()) + list(SIGNATURES_HOUSEHOLDER_COLS.items()) + list(SIGNATURES_HOUSEHOLDER.items())
+                              + list(SIGNATURES_SYLVESTER_COLS.items())):
         fn = getattr(lib, name)
         fn.restype = res
         fn.argtypes = args

@@ -30,7 +30,7 @@ from . import _lib as L
 __all__ = [
     "Transform", "Bijector", "Inverse", "ComposedFunction", "Elementwise", "elementwise", "exp", "log", "identity",
     "Shift", "Scale", "Logit", "LeakyReLU", "TruncatedBijector", "SignFlip", "OrderedBijector", "SimplexBijector",
-    "VecCholeskyBijector", "VecCorrBijector", "CorrBijector", "PDBijector", "PDVecBijector", "Permute", "PlanarLayer", "AmortizedPlanarLayer", "RadialLayer", "AmortizedRadialLayer", "AmortizedHouseholderFlow", "HouseholderLayer", "InvertibleBatchNorm", "RationalQuadraticSpline",
+    "VecCholeskyBijector", "VecCorrBijector", "CorrBijector", "PDBijector", "PDVecBijector", "Permute", "PlanarLayer", "AmortizedPlanarLayer", "RadialLayer", "AmortizedRadialLayer", "AmortizedHouseholderFlow", "HouseholderLayer", "AmortizedSylvesterLayer", "InvertibleBatchNorm", "RationalQuadraticSpline",
     "PartitionMask", "Coupling", "Stacked", "NamedStacked", "Columnwise", "columnwise", "vjp", "istraining", "training", "transform", "inverse", "logabsdetjac", "with_logabsdet_jacobian",
     "with_logabsdet_jacobian_", "transform_", "output_size", "isinvertible", "isclosedform", "colmajor", "context", "_fast_plans",
     "PlanarResult", "vjp_params", "row_moments", "MvNormal", "TorchBase", "TransformedDistribution", "transformed", "logpdf", "logpdf_vjp_params", "rand",
@@ -444,7 +444,7 @@ def isinvertible(t) -> bool:  # interface.jl:238,273
 def isclosedform(t) -> bool:  # interface.jl:231 ; planar_layer.jl:188 ; composed.jl:2
     if isinstance(t, ComposedFunction):
         return isclosedform(t.inner) and isclosedform(t.outer)
-    if isinstance(t, Inverse) and isinstance(t.orig, (PlanarLayer, AmortizedPlanarLayer)):
+    if isinstance(t, Inverse) and isinstance(t.orig, (PlanarLayer, AmortizedPlanarLayer, AmortizedSylvesterLayer)):
         return False
     return True
 
@@ -1948,6 +1948,116 @@ class AmortizedHouseholderFlow(Bijector):
         return xb, grads
 
 
+class AmortizedSylvesterLayer(Bijector):
+    """One Sylvester layer with its parameters per COLUMN of the batch — the amortised Sylvester flow of van den Berg, Hasenclever,
+    Tomczak & Welling (2018), the planar map widened to M hidden units, where an encoder emits (Q, R, R̃, b) for every sample
+    (include/bjx_sylvester_cols.h):
+
+        s = Qᵀz;   a = tanh(triu(R̃) s + b);   y = z + Q triu(R) a;   logabsdetjac = Σ_m log|1 + (1 − a_m²) R̃_mm R_mm|
+
+    Only the upper triangles of `r` and `r_tilde` (diagonal included) are read.  The log-det is the Jacobian's only when QᵀQ = I:
+    orthogonalising `q` is the caller's job; the kernels evaluate these forms for any q, and `vjp_params` treats q as a free parameter.
+
+    `q`: (dim, M, batch), or (dim, batch) for M = 1; `r`, `r_tilde`: (M, M, batch), or (batch,) at M = 1; `b`: (M, batch), or (batch,) at
+    M = 1.  Tensors already laid out column-major per column — a `permute(2, 1, 0)` view of a (batch, M, dim) network output, or slices
+    of one head [dim·M + 2M² + M, batch] — are passed with their column stride and no copy.  `vjp_params` returns the cotangents of q,
+    r, r_tilde, b per column, with the shapes given here (the strict lower triangles of r̄ and r̃̄ are zeros).  A stack of K layers is
+    written l_K @ … @ l_1.  The inverse map is not built: `inverse(layer)` applied to data raises NotImplementedError.  M <= 16, M <= dim,
+    dim <= 1 024 in Float32 and 512 in Float64 (ValueError otherwise)."""
+
+    MAX_DIM = {torch.float32: 1024, torch.float64: 512}
+
+    def __init__(self, q, r, r_tilde, b):
+        self.q, self.r, self.r_tilde, self.b = torch.as_tensor(q), torch.as_tensor(r), torch.as_tensor(r_tilde), torch.as_tensor(b)
+        if self.q.dim() not in (2, 3):
+            raise ValueError("DimensionMismatch: expected q of shape (dim, batch) or (dim, M, batch)")
+        self.n_units = 1 if self.q.dim() == 2 else int(self.q.shape[1])
+        self.dim, self.batch = int(self.q.shape[0]), int(self.q.shape[-1])
+        M = self.n_units
+        if not 1 <= M <= L.BJX_SYLVESTER_COLS_MAX_UNITS:
+            raise ValueError(f"AmortizedSylvesterLayer: {M} hidden units (1 ... {L.BJX_SYLVESTER_COLS_MAX_UNITS} supported)")
+        if M > self.dim:
+            raise ValueError(f"AmortizedSylvesterLayer: {M} hidden units above dim {self.dim}")
+        for name, t in (("r", self.r), ("r_tilde", self.r_tilde)):
+            if tuple(t.shape) != (M, M, self.batch) and not (M == 1 and tuple(t.shape) == (self.batch,)):
+                raise ValueError(f"DimensionMismatch: expected {name} of shape ({M}, {M}, {self.batch})" + (f" or ({self.batch},)" if M == 1 else ""))
+        if tuple(self.b.shape) != (M, self.batch) and not (M == 1 and tuple(self.b.shape) == (self.batch,)):
+            raise ValueError(f"DimensionMismatch: expected b of shape ({M}, {self.batch})" + (f" or ({self.batch},)" if M == 1 else ""))
+
+    def _key(self):
+        return (_keyify(self.q), _keyify(self.r), _keyify(self.r_tilde), _keyify(self.b))
+
+    def _col_params(self, like, dim, batch):
+        """-> (p_q, p_r, p_rt, p_b, ld_q, ld_r, ld_rt, ld_b) for bjx_sylvester_cols: q column-major per column ([r + m*dim + col*ld]), r
+        and r_tilde as [i + j*M + col*ld], b as [m + col*ld]; a tensor already laid out so is passed as it is, anything else is made so
+        once (the rule of AmortizedPlanarLayer._col_params)."""
+        if dim != self.dim:
+            raise ValueError(f"DimensionMismatch: AmortizedSylvesterLayer of dimension {self.dim} applied to {dim} rows")
+        if batch != self.batch:
+            raise ValueError(f"DimensionMismatch: Sylvester parameters for {self.batch} columns applied to {batch} columns")
+        if dim > self.MAX_DIM.get(like.dtype, 0):
+            raise ValueError(f"AmortizedSylvesterLayer: dim {dim} above the {self.MAX_DIM.get(like.dtype, 0)} rows supported in {like.dtype}")
+        M = self.n_units
+        outs, lds = [], []
+        for t, rows in ((self.q, dim), (self.r, M), (self.r_tilde, M)):
+            t = t.detach().to(device=like.device, dtype=like.dtype)
+            t = t.unsqueeze(1) if t.dim() == 2 else (t.reshape(1, 1, batch) if t.dim() == 1 else t)
+            ok = (t.stride(0) == 1 or rows <= 1) and (t.stride(1) == rows or M <= 1) and (t.stride(2) >= rows * M or batch <= 1)
+            if not ok:
+                t = t.permute(2, 1, 0).contiguous().permute(2, 1, 0)
+            outs.append(t)
+            lds.append(int(t.stride(2)) if batch > 1 else rows * M)
+        t = self.b.detach().to(device=like.device, dtype=like.dtype)
+        t = t.unsqueeze(0) if t.dim() == 1 else t
+        if not ((t.stride(0) == 1 or M <= 1) and (t.stride(1) >= M or batch <= 1)):
+            t = t.T.contiguous().T
+        outs.append(t)
+        lds.append(int(t.stride(1)) if batch > 1 else M)
+        return outs + lds
+
+    def _wlj(self, x, per_sample, want_ladj=True):
+        xc, dim, batch, vec = _prep(x)
+        pq, pr, prt, pb, lq, lr, lrt, lb = self._col_params(xc, dim, batch)
+        try:
+            return _call_struct("bjx_sylvester_cols", x, dim, True, per_sample, want_ladj,
+                                (_ptr(pq), _ptr(pr), _ptr(prt), _ptr(pb), lq, lr, lrt, lb, self.n_units), (dim,))
+        except NotImplementedError as e:                # BJX_ERR_UNSUPPORTED: a size limit of the entry, named in its message
+            raise ValueError(str(e)) from None
+
+    def _wlj_inv(self, x, per_sample, want_ladj=True):
+        raise NotImplementedError("inverse(AmortizedSylvesterLayer): the inverse map is not built (M scalar monotone equations solved by "
+                                  "back-substitution, DESIGN.md §9)")
+
+    def _pullback(self, x, out_bar, ladj_bar, inv, params):
+        """One bjx_sylvester_cols_vjp launch: -> (x_bar, {"q", "r", "r_tilde", "b"} per column with the constructor's shapes, or None)."""
+        if inv:
+            self._wlj_inv(x, True)
+        xc, dim, batch, vec = _prep(x)
+        gc, gdim, gbatch, _ = _prep(out_bar)
+        if (gdim, gbatch) != (dim, batch) or gc.dtype != xc.dtype:
+            raise ValueError("DimensionMismatch: out_bar must have the shape and dtype of the output")
+        pq, pr, prt, pb, lq, lr, lrt, ldb = self._col_params(xc, dim, batch)
+        lb = _ladj_bar(ladj_bar, batch, xc)
+        ctx = context(xc.device)
+        xb = _empty(dim, batch, xc, vec)
+        M = self.n_units
+        qb = rb = rtb = bb = None
+        if params:
+            qb = torch.empty((batch, M, dim), dtype=xc.dtype, device=xc.device).permute(2, 1, 0)
+            rb, rtb = (torch.empty((batch, M, M), dtype=xc.dtype, device=xc.device).permute(2, 1, 0) for _ in range(2))
+            bb = torch.empty((batch, M), dtype=xc.dtype, device=xc.device).T
+        rc = L.load().bjx_sylvester_cols_vjp(ctx.h, _dt(xc), _ptr(pq), _ptr(pr), _ptr(prt), _ptr(pb), lq, lr, lrt, ldb, M, _ptr(xc), _ptr(gc), _ptr(lb),
+                                             _ptr(xb), _ptr(qb), _ptr(rb), _ptr(rtb), _ptr(bb), dim, batch)
+        try:
+            L.check(ctx.h, rc, "bjx_sylvester_cols_vjp")
+        except NotImplementedError as e:                # BJX_ERR_UNSUPPORTED: a size limit of the entry, named in its message
+            raise ValueError(str(e)) from None
+        if not params:
+            return xb, None
+        return xb, {"q": qb[:, 0, :] if self.q.dim() == 2 else qb, "r": rb[0, 0] if self.r.dim() == 1 else rb,
+                    "r_tilde": rtb[0, 0] if self.r_tilde.dim() == 1 else rtb, "b": bb[0] if self.b.dim() == 1 else bb}
+
+
 _HH_LDS_REFUSED: set = set()      # (dtype, dim, n_layers) whose Float64 tables bjx_householder_vjp_params refused: they take the chunked fallback
 _HH_FALLBACK_ELEMS = 1 << 25      # elements of the expanded v (and of the per-column v̄) one chunk of the fallback holds
 
@@ -3372,7 +3482,7 @@ def vjp(b, x, out_bar, ladj_bar=None):
         rc = L.load().bjx_planar_vjp(ctx.h, _dt(xc), int(inv), _ptr(w), _ptr(u), _ptr(bb), base.n_layers, _ptr(xc), _ptr(gc), _ptr(lb), _ptr(xb), dim, batch)
         L.check(ctx.h, rc, "bjx_planar_vjp")
         return xb
-    if isinstance(base, (AmortizedPlanarLayer, AmortizedRadialLayer, AmortizedHouseholderFlow)):     # per-column parameters: one bjx_planar_cols_vjp / bjx_radial_cols_vjp / bjx_householder_cols_vjp launch, either direction
+    if isinstance(base, (AmortizedPlanarLayer, AmortizedRadialLayer, AmortizedHouseholderFlow, AmortizedSylvesterLayer)):     # per-column parameters: one bjx_planar_cols_vjp / bjx_radial_cols_vjp / bjx_householder_cols_vjp / bjx_sylvester_cols_vjp launch, either direction (Sylvester: forward only)
         return base._pullback(x, out_bar, ladj_bar, inv, False)[0]
     if isinstance(base, HouseholderLayer):
         # y = U x with U orthogonal and symmetric factors: x̄ = Uᵀȳ = the other direction's map of ȳ (log-det 0: ladj_bar adds nothing)
@@ -3554,7 +3664,7 @@ def _vjp_composed(b, x, out_bar, ladj_bar=None):
 
 def _has_own_params(st):
     base = st.orig if isinstance(st, Inverse) else st
-    return isinstance(base, (PlanarLayer, AmortizedPlanarLayer, RadialLayer, AmortizedRadialLayer, AmortizedHouseholderFlow, HouseholderLayer, RationalQuadraticSpline, InvertibleBatchNorm))
+    return isinstance(base, (PlanarLayer, AmortizedPlanarLayer, RadialLayer, AmortizedRadialLayer, AmortizedHouseholderFlow, HouseholderLayer, AmortizedSylvesterLayer, RationalQuadraticSpline, InvertibleBatchNorm))
 
 
 def _radial_runs_unfused(b):
@@ -3865,6 +3975,7 @@ def vjp_params(b, x, out_bar, ladj_bar=None):
     For an AmortizedRadialLayer or its inverse: (x_bar, {"alpha_", "beta", "z_0"}) PER COLUMN, not summed, one launch in either direction.
     For an AmortizedHouseholderFlow or its inverse: (x_bar, {"v", "log_scale", "shift"}) PER COLUMN, not summed, one launch in either direction;
     the key of an absent parameter is omitted.
+    For an AmortizedSylvesterLayer: (x_bar, {"q", "r", "r_tilde", "b"}) PER COLUMN, not summed, one launch (its inverse is not built: NotImplementedError).
     For a HouseholderLayer or its inverse: (x_bar, {"v"}) summed over the batch, with the constructor's shape (bjx_householder_vjp_params).
     For a RationalQuadraticSpline or its inverse: (x_bar, {"widths", "heights", "derivatives"[, "raw_widths", ...]}) — see _vjp_params_rqs
     (a per-column spline, 3-D parameters: the per-column cotangents in its own form, see _rqs_cols_pullback).
@@ -3881,8 +3992,8 @@ def vjp_params(b, x, out_bar, ladj_bar=None):
     if isinstance(b, Coupling) or (isinstance(b, Inverse) and isinstance(b.orig, Coupling)):
         inv = isinstance(b, Inverse)
         return (b.orig if inv else b)._vjp(x, out_bar, ladj_bar, inv, params=True)
-    if isinstance(b, (AmortizedRadialLayer, AmortizedHouseholderFlow)) or (isinstance(b, Inverse) and isinstance(b.orig, (AmortizedRadialLayer, AmortizedHouseholderFlow))):
-        inv = isinstance(b, Inverse)                    # (x_bar, {"alpha_", "beta", "z_0"} / {"v", "log_scale", "shift"}) PER COLUMN: one launch in either direction
+    if isinstance(b, (AmortizedRadialLayer, AmortizedHouseholderFlow, AmortizedSylvesterLayer)) or (isinstance(b, Inverse) and isinstance(b.orig, (AmortizedRadialLayer, AmortizedHouseholderFlow, AmortizedSylvesterLayer))):
+        inv = isinstance(b, Inverse)                    # (x_bar, {"alpha_", "beta", "z_0"} / {"v", "log_scale", "shift"} / {"q", "r", "r_tilde", "b"}) PER COLUMN: one launch in either direction (Sylvester: forward only)
         return (b.orig if inv else b)._pullback(x, out_bar, ladj_bar, inv, True)
     if isinstance(b, HouseholderLayer) or (isinstance(b, Inverse) and isinstance(b.orig, HouseholderLayer)):
         inv = isinstance(b, Inverse)                    # (x_bar, {"v"}) summed over the batch: one pass and its folds, either direction
@@ -4385,7 +4496,7 @@ def logpdf(td: TransformedDistribution, y, reference_shape: bool = False):
 
 
 # ------------------------------------------------------------------ log-density of a transformed distribution, value AND gradients
-_PARAM_STAGES = ("PlanarLayer", "_PlanarRun", "AmortizedPlanarLayer", "RadialLayer", "AmortizedRadialLayer", "AmortizedHouseholderFlow", "HouseholderLayer", "_RadialRun", "RationalQuadraticSpline", "InvertibleBatchNorm", "Coupling", "Scale", "Shift", "Logit",
+_PARAM_STAGES = ("PlanarLayer", "_PlanarRun", "AmortizedPlanarLayer", "RadialLayer", "AmortizedRadialLayer", "AmortizedHouseholderFlow", "HouseholderLayer", "AmortizedSylvesterLayer", "_RadialRun", "RationalQuadraticSpline", "InvertibleBatchNorm", "Coupling", "Scale", "Shift", "Logit",
                  "LeakyReLU")
 
 
