@@ -238,10 +238,25 @@ SIGNATURES_SYLVESTER_COLS = {
     "bjx_sylvester_cols_vjp": (_i, [_vp, _i, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64]),
 }
 
+# include/bjx_sylvester.h (one Sylvester layer with ONE (Q, R, R~, b) shared by every column): q T[dim, M], r, r_tilde T[M, M], b T[M], M, then
+# the data as bjx_radial; the pullback takes in, out_bar, ladj_bar (may be NULL), in_bar (may be NULL) and q_bar, r_bar, rt_bar, b_bar summed
+# over the batch (all four or none: none is the plain input pullback)
+BJX_SYLVESTER_MAX_UNITS = 16
+BJX_SYLVESTER_LDS_BUDGET = 65536
+SIGNATURES_SYLVESTER = {
+    "bjx_sylvester": (_i, [_vp, _i, _vp, _vp, _vp, _vp, _i, _vp, _vp] + _tail),
+    "bjx_sylvester_vjp_params": (_i, [_vp, _i, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64]),
+}
+
 
 def householder_lds_bytes(dim: int, n_layers: int) -> int:
     """BJX_HOUSEHOLDER_LDS_BYTES of include/bjx_householder.h: four Float64 tables [n_layers][dim + 1] and n_layers values t_k."""
     return 8 * n_layers * (4 * (dim + 1) + 1)
+
+
+def sylvester_lds_bytes(dim: int, M: int) -> int:
+    """BJX_SYLVESTER_LDS_BYTES of include/bjx_sylvester.h: four Float64 tables of dim*M + 2*M*M + M entries."""
+    return 32 * (dim * M + 2 * M * M + M)
 
 
 _lib = None
@@ -260,14 +275,14 @@ def load() -> C.CDLL:
     lib = C.CDLL(LIB_PATH, mode=C.RTLD_GLOBAL)
     missing = [n for n in list(SIGNATURES) + list(SIGNATURES_COLS) + list(SIGNATURES_COUPLING) + list(SIGNATURES_CHAIN_VJP) + list(SIGNATURES_RADIAL_STACK)
                + list(SIGNATURES_RADIAL_STACK_PARAMS) + list(SIGNATURES_RADIAL_STACK_LOGPDF) + list(SIGNATURES_PLANAR_LOGPDF) + list(SIGNATURES_PLANAR_COLS)
-               + list(SIGNATURES_RADIAL_COLS) + list(SIGNATURES_HOUSEHOLDER_COLS) + list(SIGNATURES_HOUSEHOLDER) + list(SIGNATURES_SYLVESTER_COLS) if not hasattr(lib, n)]
+               + list(SIGNATURES_RADIAL_COLS) + list(SIGNATURES_HOUSEHOLDER_COLS) + list(SIGNATURES_HOUSEHOLDER) + list(SIGNATURES_SYLVESTER_COLS) + list(SIGNATURES_SYLVESTER) if not hasattr(lib, n)]
     if missing:  # an incomplete ABI is a build error, not something to paper over
         raise ImportError(f"{LIB_PATH} does not export {missing}; rebuild it")
     for name, (res, args) in (list(SIGNATURES.items()) + list(SIGNATURES_COLS.items()) + list(SIGNATURES_COUPLING.items())
                               + list(SIGNATURES_CHAIN_VJP.items()) + list(SIGNATURES_RADIAL_STACK.items()) + list(SIGNATURES_RADIAL_STACK_PARAMS.items())
                               + list(SIGNATURES_RADIAL_STACK_LOGPDF.items()) + list(SIGNATURES_PLANAR_LOGPDF.items()) + list(SIGNATURES_PLANAR_COLS.items())
                               + list(SIGNATURES_RADIAL_COLS.items()) + list(SIGNATURES_HOUSEHOLDER_COLS.items()) + list(SIGNATURES_HOUSEHOLDER.items())
-                              + list(SIGNATURES_SYLVESTER_COLS.items())):
+                              + list(SIGNATURES_SYLVESTER_COLS.items()) + list(SIGNATURES_SYLVESTER.items())):
         fn = getattr(lib, name)
         fn.restype = res
         fn.argtypes = args

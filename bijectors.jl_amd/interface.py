@@ -30,7 +30,7 @@ from . import _lib as L
 __all__ = [
     "Transform", "Bijector", "Inverse", "ComposedFunction", "Elementwise", "elementwise", "exp", "log", "identity",
     "Shift", "Scale", "Logit", "LeakyReLU", "TruncatedBijector", "SignFlip", "OrderedBijector", "SimplexBijector",
-    "VecCholeskyBijector", "VecCorrBijector", "CorrBijector", "PDBijector", "PDVecBijector", "Permute", "PlanarLayer", "AmortizedPlanarLayer", "RadialLayer", "AmortizedRadialLayer", "AmortizedHouseholderFlow", "HouseholderLayer", "AmortizedSylvesterLayer", "InvertibleBatchNorm", "RationalQuadraticSpline",
+    "VecCholeskyBijector", "VecCorrBijector", "CorrBijector", "PDBijector", "PDVecBijector", "Permute", "PlanarLayer", "AmortizedPlanarLayer", "RadialLayer", "AmortizedRadialLayer", "AmortizedHouseholderFlow", "HouseholderLayer", "AmortizedSylvesterLayer", "SylvesterLayer", "InvertibleBatchNorm", "RationalQuadraticSpline",
     "PartitionMask", "Coupling", "Stacked", "NamedStacked", "Columnwise", "columnwise", "vjp", "istraining", "training", "transform", "inverse", "logabsdetjac", "with_logabsdet_jacobian",
     "with_logabsdet_jacobian_", "transform_", "output_size", "isinvertible", "isclosedform", "colmajor", "context", "_fast_plans",
     "PlanarResult", "vjp_params", "row_moments", "MvNormal", "TorchBase", "TransformedDistribution", "transformed", "logpdf", "logpdf_vjp_params", "rand",
@@ -444,7 +444,7 @@ def isinvertible(t) -> bool:  # interface.jl:238,273
 def isclosedform(t) -> bool:  # interface.jl:231 ; planar_layer.jl:188 ; composed.jl:2
     if isinstance(t, ComposedFunction):
         return isclosedform(t.inner) and isclosedform(t.outer)
-    if isinstance(t, Inverse) and isinstance(t.orig, (PlanarLayer, AmortizedPlanarLayer, AmortizedSylvesterLayer)):
+    if isinstance(t, Inverse) and isinstance(t.orig, (PlanarLayer, AmortizedPlanarLayer, AmortizedSylvesterLayer, SylvesterLayer)):
         return False
     return True
 
@@ -2158,6 +2158,132 @@ class HouseholderLayer(Bijector):
         return acc.to(xc.dtype).T
 
 
+_SYL_LDS_REFUSED: set = set()     # (dtype, dim, M) whose Float64 tables bjx_sylvester_vjp_params refused: they take the chunked fallback
+_SYL_FALLBACK_ELEMS = 1 << 25     # elements of the expanded q (and of the per-column q̄) one chunk of the fallback holds
+
+
+class SylvesterLayer(Bijector):
+    """One Sylvester layer with ONE parameter set shared by every column (include/bjx_sylvester.h) — the Sylvester flow of van den Berg,
+    Hasenclever, Tomczak & Welling (2018) as it is trained outside a VAE and as it sits between coupling layers; the shared half of the
+    pair whose per-column half is AmortizedSylvesterLayer:
+
+        s = Qᵀz;   a = tanh(triu(R̃) s + b);   y = z + Q triu(R) a;   logabsdetjac = Σ_m log|1 + (1 − a_m²) R̃_mm R_mm|
+
+    Only the upper triangles of `r` and `r_tilde` (diagonal included) are read.  The log-det is the Jacobian's only when QᵀQ = I:
+    orthogonalising `q` is the caller's job; the kernels evaluate these forms for any q, and `vjp_params` treats q as a free parameter.
+
+    `q`: (dim, M), or (dim,) for M = 1; `r`, `r_tilde`: (M, M), or one element at M = 1; `b`: (M,), or one element at M = 1.  `vjp` is
+    one launch; `vjp_params` returns (x_bar, {"q", "r", "r_tilde", "b"}) with the constructor's shapes, SUMMED over the batch (the strict
+    lower triangles of r̄ and r̃̄ are zeros): one streaming pass and one or two folds (bjx_sylvester_vjp_params).  Where that entry
+    refuses because its Float64 tables exceed the LDS budget (`_lib.sylvester_lds_bytes(dim, M)` above 64 KiB) the parameters are
+    expanded over chunks of columns, the chunks go through bjx_sylvester_cols_vjp and their per-column cotangents are summed in Float64
+    in a fixed order; the expanded q and the per-column q̄ of a chunk hold at most 2²⁵ elements each.  The inverse map is not built:
+    `inverse(layer)` applied to data raises NotImplementedError.  M <= 16, M <= dim, dim <= 1 024 in Float32 and 512 in Float64
+    (ValueError otherwise)."""
+
+    MAX_DIM = {torch.float32: 1024, torch.float64: 512}
+
+    def __init__(self, q, r, r_tilde, b):
+        self.q, self.r, self.r_tilde, self.b = torch.as_tensor(q), torch.as_tensor(r), torch.as_tensor(r_tilde), torch.as_tensor(b)
+        if self.q.dim() not in (1, 2):
+            raise ValueError("DimensionMismatch: expected q of shape (dim,) or (dim, M)")
+        self.dim = int(self.q.shape[0])
+        self.n_units = 1 if self.q.dim() == 1 else int(self.q.shape[1])
+        M = self.n_units
+        if self.dim < 1:
+            raise ValueError("DimensionMismatch: expected q with at least one row")
+        if not 1 <= M <= L.BJX_SYLVESTER_MAX_UNITS:
+            raise ValueError(f"SylvesterLayer: {M} hidden units (1 ... {L.BJX_SYLVESTER_MAX_UNITS} supported)")
+        if M > self.dim:
+            raise ValueError(f"SylvesterLayer: {M} hidden units above dim {self.dim}")
+        for name, t in (("r", self.r), ("r_tilde", self.r_tilde)):
+            if tuple(t.shape) != (M, M) and not (M == 1 and t.numel() == 1):
+                raise ValueError(f"DimensionMismatch: expected {name} of shape ({M}, {M})" + (" or one element" if M == 1 else ""))
+        if tuple(self.b.shape) != (M,) and not (M == 1 and self.b.numel() == 1):
+            raise ValueError(f"DimensionMismatch: expected b of shape ({M},)" + (" or one element" if M == 1 else ""))
+
+    def _key(self):
+        return (_keyify(self.q), _keyify(self.r), _keyify(self.r_tilde), _keyify(self.b))
+
+    def _tables(self, like, dim):
+        """-> (q, r, r_tilde, b) on the device, dense: q T[dim, M] (unit m at q + m*dim), r and r_tilde T[M, M] column-major, b T[M]."""
+        if dim != self.dim:
+            raise ValueError(f"DimensionMismatch: SylvesterLayer of dimension {self.dim} applied to {dim} rows")
+        if dim > self.MAX_DIM.get(like.dtype, 0):
+            raise ValueError(f"SylvesterLayer: dim {dim} above the {self.MAX_DIM.get(like.dtype, 0)} rows supported in {like.dtype}")
+        M = self.n_units
+        return (colmajor(_param(self.q, like)), colmajor(_param(self.r, like).reshape(M, M)), colmajor(_param(self.r_tilde, like).reshape(M, M)),
+                _param(self.b, like).reshape(M).contiguous())
+
+    def _wlj(self, x, per_sample, want_ladj=True):
+        xc, dim, batch, vec = _prep(x)
+        q, r, rt, b = self._tables(xc, dim)
+        return _call_struct("bjx_sylvester", x, dim, True, per_sample, want_ladj, (_ptr(q), _ptr(r), _ptr(rt), _ptr(b), self.n_units), (dim,))
+
+    def _wlj_inv(self, x, per_sample, want_ladj=True):
+        raise NotImplementedError("inverse(SylvesterLayer): the inverse map is not built (M scalar monotone equations solved by "
+                                  "back-substitution, DESIGN.md §9)")
+
+    def _shaped(self, qb, rb, rtb, bb):
+        return {"q": qb.reshape(self.q.shape), "r": rb.reshape(self.r.shape), "r_tilde": rtb.reshape(self.r_tilde.shape), "b": bb.reshape(self.b.shape)}
+
+    def _pullback(self, x, out_bar, ladj_bar, inv, params):
+        """-> (x_bar, {"q", "r", "r_tilde", "b"} summed over the batch with the constructor's shapes, or None): bjx_sylvester_vjp_params, its
+        all-NULL form (one launch) when `params` is false."""
+        if inv:
+            self._wlj_inv(x, True)
+        xc, dim, batch, vec = _prep(x)
+        gc, gdim, gbatch, _ = _prep(out_bar)
+        if (gdim, gbatch) != (dim, batch) or gc.dtype != xc.dtype:
+            raise ValueError("DimensionMismatch: out_bar must have the shape and dtype of the output")
+        q, r, rt, b = self._tables(xc, dim)
+        lb = _ladj_bar(ladj_bar, batch, xc)
+        ctx = context(xc.device)
+        xb = _empty(dim, batch, xc, vec)
+        M = self.n_units
+        fn = L.load().bjx_sylvester_vjp_params
+        if not params:
+            rc = fn(ctx.h, _dt(xc), _ptr(q), _ptr(r), _ptr(rt), _ptr(b), M, _ptr(xc), _ptr(gc), _ptr(lb), _ptr(xb), None, None, None, None, dim, batch)
+            L.check(ctx.h, rc, "bjx_sylvester_vjp_params")
+            return xb, None
+        key = (xc.dtype, dim, M)
+        if key not in _SYL_LDS_REFUSED:
+            qb = torch.empty((M, dim), dtype=xc.dtype, device=xc.device).T
+            rb, rtb = (torch.empty((M, M), dtype=xc.dtype, device=xc.device).T for _ in range(2))
+            bb = torch.empty(M, dtype=xc.dtype, device=xc.device)
+            rc = fn(ctx.h, _dt(xc), _ptr(q), _ptr(r), _ptr(rt), _ptr(b), M, _ptr(xc), _ptr(gc), _ptr(lb), _ptr(xb), _ptr(qb), _ptr(rb), _ptr(rtb), _ptr(bb), dim, batch)
+            if rc != L.ERR_UNSUPPORTED:
+                L.check(ctx.h, rc, "bjx_sylvester_vjp_params")
+                return xb, self._shaped(qb, rb, rtb, bb)
+            _SYL_LDS_REFUSED.add(key)                   # the sizes were checked above: only the LDS rule is left
+        return xb, self._shaped(*self._vjp_params_chunked(ctx, q, r, rt, b, xc, gc, lb, xb, dim, batch))
+
+    def _vjp_params_chunked(self, ctx, q, r, rt, b, xc, gc, lb, xb, dim, batch):
+        """The fallback of `_pullback`: chunks of columns with the parameters expanded per column through bjx_sylvester_cols_vjp, the
+        per-column cotangents summed over each chunk and the chunks added in order, in Float64 (torch's sum over one axis has a fixed
+        order).  Scratch: the expanded q and the per-column q̄ of one chunk, `_SYL_FALLBACK_ELEMS` elements each at the most."""
+        M = self.n_units
+        sizes = (dim * M, M * M, M * M, M)
+        chunk = max(1, _SYL_FALLBACK_ELEMS // (dim * M))
+        accs = [torch.zeros(n, dtype=torch.float64, device=xc.device) for n in sizes]
+        esz = xc.element_size()
+        flat = [t.T.reshape(1, -1) if t.dim() == 2 else t.reshape(1, -1) for t in (q, r, rt, b)]      # the dense tables as rows
+        for lo in range(0, batch, chunk):
+            n = min(chunk, batch - lo)
+            exp = [f.expand(n, f.shape[1]).contiguous() for f in flat]
+            outs = [torch.empty((n, k), dtype=xc.dtype, device=xc.device) for k in sizes]
+            off = lo * dim * esz
+            lbp = None if lb is None else C.c_void_p(lb.data_ptr() + lo * esz)
+            rc = L.load().bjx_sylvester_cols_vjp(ctx.h, _dt(xc), _ptr(exp[0]), _ptr(exp[1]), _ptr(exp[2]), _ptr(exp[3]), *sizes, M, C.c_void_p(xc.data_ptr() + off),
+                                                 C.c_void_p(gc.data_ptr() + off), lbp, C.c_void_p(xb.data_ptr() + off), _ptr(outs[0]), _ptr(outs[1]), _ptr(outs[2]),
+                                                 _ptr(outs[3]), dim, n)
+            L.check(ctx.h, rc, "bjx_sylvester_cols_vjp")
+            for acc, o in zip(accs, outs):
+                acc += o.to(torch.float64).sum(dim=0)
+        qb, rb, rtb, bb = (acc.to(xc.dtype) for acc in accs)
+        return qb.reshape(M, dim).T, rb.reshape(M, M).T, rtb.reshape(M, M).T, bb
+
+
 class RadialLayer(Bijector):
     """radial_layer.jl:11-133"""
 
@@ -3484,6 +3610,8 @@ def vjp(b, x, out_bar, ladj_bar=None):
         return xb
     if isinstance(base, (AmortizedPlanarLayer, AmortizedRadialLayer, AmortizedHouseholderFlow, AmortizedSylvesterLayer)):     # per-column parameters: one bjx_planar_cols_vjp / bjx_radial_cols_vjp / bjx_householder_cols_vjp / bjx_sylvester_cols_vjp launch, either direction (Sylvester: forward only)
         return base._pullback(x, out_bar, ladj_bar, inv, False)[0]
+    if isinstance(base, SylvesterLayer):             # shared parameters: the all-NULL form of bjx_sylvester_vjp_params, one launch (forward only)
+        return base._pullback(x, out_bar, ladj_bar, inv, False)[0]
     if isinstance(base, HouseholderLayer):
         # y = U x with U orthogonal and symmetric factors: x̄ = Uᵀȳ = the other direction's map of ȳ (log-det 0: ladj_bar adds nothing)
         if tuple(out_bar.shape) != tuple(x.shape) or out_bar.dtype != x.dtype:
@@ -3664,7 +3792,7 @@ def _vjp_composed(b, x, out_bar, ladj_bar=None):
 
 def _has_own_params(st):
     base = st.orig if isinstance(st, Inverse) else st
-    return isinstance(base, (PlanarLayer, AmortizedPlanarLayer, RadialLayer, AmortizedRadialLayer, AmortizedHouseholderFlow, HouseholderLayer, AmortizedSylvesterLayer, RationalQuadraticSpline, InvertibleBatchNorm))
+    return isinstance(base, (PlanarLayer, AmortizedPlanarLayer, RadialLayer, AmortizedRadialLayer, AmortizedHouseholderFlow, HouseholderLayer, AmortizedSylvesterLayer, SylvesterLayer, RationalQuadraticSpline, InvertibleBatchNorm))
 
 
 def _radial_runs_unfused(b):
@@ -3977,6 +4105,7 @@ def vjp_params(b, x, out_bar, ladj_bar=None):
     the key of an absent parameter is omitted.
     For an AmortizedSylvesterLayer: (x_bar, {"q", "r", "r_tilde", "b"}) PER COLUMN, not summed, one launch (its inverse is not built: NotImplementedError).
     For a HouseholderLayer or its inverse: (x_bar, {"v"}) summed over the batch, with the constructor's shape (bjx_householder_vjp_params).
+    For a SylvesterLayer: (x_bar, {"q", "r", "r_tilde", "b"}) summed over the batch, with the constructor's shapes (bjx_sylvester_vjp_params; its inverse is not built: NotImplementedError).
     For a RationalQuadraticSpline or its inverse: (x_bar, {"widths", "heights", "derivatives"[, "raw_widths", ...]}) — see _vjp_params_rqs
     (a per-column spline, 3-D parameters: the per-column cotangents in its own form, see _rqs_cols_pullback).
     For a Coupling or its inverse: (x_bar, grads) with the cotangents of θ's outputs — {"scale", "shift"} per column (affine law),
@@ -3998,6 +4127,9 @@ def vjp_params(b, x, out_bar, ladj_bar=None):
     if isinstance(b, HouseholderLayer) or (isinstance(b, Inverse) and isinstance(b.orig, HouseholderLayer)):
         inv = isinstance(b, Inverse)                    # (x_bar, {"v"}) summed over the batch: one pass and its folds, either direction
         return (b.orig if inv else b)._vjp_params(x, out_bar, ladj_bar, inv)
+    if isinstance(b, SylvesterLayer) or (isinstance(b, Inverse) and isinstance(b.orig, SylvesterLayer)):
+        inv = isinstance(b, Inverse)                    # (x_bar, {"q", "r", "r_tilde", "b"}) summed over the batch: one pass and its folds (forward only)
+        return (b.orig if inv else b)._pullback(x, out_bar, ladj_bar, inv, True)
     if isinstance(b, Inverse) and isinstance(b.orig, (PlanarLayer, RadialLayer, AmortizedPlanarLayer)):
         return _vjp_params_inverse(b, x, out_bar, ladj_bar)
     if isinstance(b, AmortizedPlanarLayer):            # (x_bar, {"w", "u", "b"}) PER COLUMN, with the shapes of the constructor's arguments
@@ -4496,7 +4628,7 @@ def logpdf(td: TransformedDistribution, y, reference_shape: bool = False):
 
 
 # ------------------------------------------------------------------ log-density of a transformed distribution, value AND gradients
-_PARAM_STAGES = ("PlanarLayer", "_PlanarRun", "AmortizedPlanarLayer", "RadialLayer", "AmortizedRadialLayer", "AmortizedHouseholderFlow", "HouseholderLayer", "AmortizedSylvesterLayer", "_RadialRun", "RationalQuadraticSpline", "InvertibleBatchNorm", "Coupling", "Scale", "Shift", "Logit",
+_PARAM_STAGES = ("PlanarLayer", "_PlanarRun", "AmortizedPlanarLayer", "RadialLayer", "AmortizedRadialLayer", "AmortizedHouseholderFlow", "HouseholderLayer", "AmortizedSylvesterLayer", "SylvesterLayer", "_RadialRun", "RationalQuadraticSpline", "InvertibleBatchNorm", "Coupling", "Scale", "Shift", "Logit",
                  "LeakyReLU")
 
 
