@@ -248,6 +248,13 @@ SIGNATURES_SYLVESTER = {
     "bjx_sylvester_vjp_params": (_i, [_vp, _i, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64]),
 }
 
+# include/bjx_sylvester_inv.h (the inverse of the same layer, for QᵀQ = I): the arguments of bjx_sylvester; the pullback takes in (y), out_bar
+# (z̄), ladj_bar (may be NULL), in_bar (ȳ, may be NULL) and pre (z with the bits of the map, may be NULL)
+SIGNATURES_SYLVESTER_INV = {
+    "bjx_sylvester_inv": (_i, [_vp, _i, _vp, _vp, _vp, _vp, _i, _vp, _vp] + _tail),
+    "bjx_sylvester_inv_vjp": (_i, [_vp, _i, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _i64, _i64]),
+}
+
 
 def householder_lds_bytes(dim: int, n_layers: int) -> int:
     """BJX_HOUSEHOLDER_LDS_BYTES of include/bjx_householder.h: four Float64 tables [n_layers][dim + 1] and n_layers values t_k."""
@@ -275,14 +282,15 @@ def load() -> C.CDLL:
     lib = C.CDLL(LIB_PATH, mode=C.RTLD_GLOBAL)
     missing = [n for n in list(SIGNATURES) + list(SIGNATURES_COLS) + list(SIGNATURES_COUPLING) + list(SIGNATURES_CHAIN_VJP) + list(SIGNATURES_RADIAL_STACK)
                + list(SIGNATURES_RADIAL_STACK_PARAMS) + list(SIGNATURES_RADIAL_STACK_LOGPDF) + list(SIGNATURES_PLANAR_LOGPDF) + list(SIGNATURES_PLANAR_COLS)
-               + list(SIGNATURES_RADIAL_COLS) + list(SIGNATURES_HOUSEHOLDER_COLS) + list(SIGNATURES_HOUSEHOLDER) + list(SIGNATURES_SYLVESTER_COLS) + list(SIGNATURES_SYLVESTER) if not hasattr(lib, n)]
+               + list(SIGNATURES_RADIAL_COLS) + list(SIGNATURES_HOUSEHOLDER_COLS) + list(SIGNATURES_HOUSEHOLDER) + list(SIGNATURES_SYLVESTER_COLS) + list(SIGNATURES_SYLVESTER)
+               + list(SIGNATURES_SYLVESTER_INV) if not hasattr(lib, n)]
     if missing:  # an incomplete ABI is a build error, not something to paper over
         raise ImportError(f"{LIB_PATH} does not export {missing}; rebuild it")
     for name, (res, args) in (list(SIGNATURES.items()) + list(SIGNATURES_COLS.items()) + list(SIGNATURES_COUPLING.items())
                               + list(SIGNATURES_CHAIN_VJP.items()) + list(SIGNATURES_RADIAL_STACK.items()) + list(SIGNATURES_RADIAL_STACK_PARAMS.items())
                               + list(SIGNATURES_RADIAL_STACK_LOGPDF.items()) + list(SIGNATURES_PLANAR_LOGPDF.items()) + list(SIGNATURES_PLANAR_COLS.items())
                               + list(SIGNATURES_RADIAL_COLS.items()) + list(SIGNATURES_HOUSEHOLDER_COLS.items()) + list(SIGNATURES_HOUSEHOLDER.items())
-                              + list(SIGNATURES_SYLVESTER_COLS.items()) + list(SIGNATURES_SYLVESTER.items())):
+                              + list(SIGNATURES_SYLVESTER_COLS.items()) + list(SIGNATURES_SYLVESTER.items()) + list(SIGNATURES_SYLVESTER_INV.items())):
         fn = getattr(lib, name)
         fn.restype = res
         fn.argtypes = args

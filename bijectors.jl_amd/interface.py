@@ -2177,14 +2177,26 @@ class SylvesterLayer(Bijector):
     lower triangles of r̄ and r̃̄ are zeros): one streaming pass and one or two folds (bjx_sylvester_vjp_params).  Where that entry
     refuses because its Float64 tables exceed the LDS budget (`_lib.sylvester_lds_bytes(dim, M)` above 64 KiB) the parameters are
     expanded over chunks of columns, the chunks go through bjx_sylvester_cols_vjp and their per-column cotangents are summed in Float64
-    in a fixed order; the expanded q and the per-column q̄ of a chunk hold at most 2²⁵ elements each.  The inverse map is not built:
-    `inverse(layer)` applied to data raises NotImplementedError.  M <= 16, M <= dim, dim <= 1 024 in Float32 and 512 in Float64
-    (ValueError otherwise)."""
+    in a fixed order; the expanded q and the per-column q̄ of a chunk hold at most 2²⁵ elements each.  M <= 16, M <= dim, dim <= 1 024
+    in Float32 and 512 in Float64 (ValueError otherwise).
+
+    The inverse is opt-in.  With the default `orthonormal=False`, `inverse(layer)` applied to data raises NotImplementedError: the forms
+    above are a bijection with a known inverse only for an orthonormal q.  `orthonormal=True` is the caller's declaration that QᵀQ = I
+    and that R_mm·R̃_mm > −1 for every unit (the paper's invertibility condition, wᵀû > −1 of the planar flow); the constructor reads no
+    parameter value (no host synchronisation) — `orthonormality_defect()` is the check a caller may run.  The inverse is then served by
+    include/bjx_sylvester_inv.h: M scalar monotone equations solved from the last unit to the first by the planar flow's root solve,
+    `transform`, `with_logabsdet_jacobian`, `logabsdetjac` and their in-place forms one launch (the summed log-det one more), `vjp` one
+    launch, and `vjp_params(inverse(layer), y, z̄, c)` = (ȳ, {"q", "r", "r_tilde", "b"}) by the implicit-function rule: one launch for ȳ
+    and z, the forward parameter pullback at z with the cotangents (ȳ, c), four negations.  q̄ is the cotangent in the ambient space (q a
+    free parameter of the forward forms), as in the forward direction.  The log-det is log|d| in both directions; R_mm·R̃_mm <= −1 is not
+    refused: the root solve then returns some root inside the reference's bracket after a bounded number of steps and the values are
+    unspecified, as they are where QᵀQ differs from I."""
 
     MAX_DIM = {torch.float32: 1024, torch.float64: 512}
 
-    def __init__(self, q, r, r_tilde, b):
+    def __init__(self, q, r, r_tilde, b, orthonormal=False):
         self.q, self.r, self.r_tilde, self.b = torch.as_tensor(q), torch.as_tensor(r), torch.as_tensor(r_tilde), torch.as_tensor(b)
+        self.orthonormal = bool(orthonormal)
         if self.q.dim() not in (1, 2):
             raise ValueError("DimensionMismatch: expected q of shape (dim,) or (dim, M)")
         self.dim = int(self.q.shape[0])
@@ -2220,18 +2232,54 @@ class SylvesterLayer(Bijector):
         q, r, rt, b = self._tables(xc, dim)
         return _call_struct("bjx_sylvester", x, dim, True, per_sample, want_ladj, (_ptr(q), _ptr(r), _ptr(rt), _ptr(b), self.n_units), (dim,))
 
+    def orthonormality_defect(self) -> float:
+        """max |QᵀQ − I| computed in Float64.  Synchronises with the device (the result is a Python float): the check a caller runs
+        before, or instead of trusting, `orthonormal=True`; nothing in the layer calls it."""
+        q = self.q.detach().to(torch.float64).reshape(self.dim, self.n_units)
+        eye = torch.eye(self.n_units, dtype=torch.float64, device=q.device)
+        return float((q.T @ q - eye).abs().max())
+
+    def _refuse_inverse(self):
+        if not self.orthonormal:
+            raise NotImplementedError("inverse(SylvesterLayer): the inverse map is not built for a layer with a general q (the forms are inverted by M "
+                                      "scalar monotone equations only where QᵀQ = I): construct the layer with orthonormal=True to declare QᵀQ = I "
+                                      "and R_mm·R̃_mm > −1, DESIGN.md §9")
+
     def _wlj_inv(self, x, per_sample, want_ladj=True):
-        raise NotImplementedError("inverse(SylvesterLayer): the inverse map is not built (M scalar monotone equations solved by "
-                                  "back-substitution, DESIGN.md §9)")
+        self._refuse_inverse()
+        xc, dim, batch, vec = _prep(x)
+        q, r, rt, b = self._tables(xc, dim)
+        return _call_struct("bjx_sylvester_inv", x, dim, True, per_sample, want_ladj, (_ptr(q), _ptr(r), _ptr(rt), _ptr(b), self.n_units), (dim,))
 
     def _shaped(self, qb, rb, rtb, bb):
         return {"q": qb.reshape(self.q.shape), "r": rb.reshape(self.r.shape), "r_tilde": rtb.reshape(self.r_tilde.shape), "b": bb.reshape(self.b.shape)}
 
+    def _pullback_inv(self, y, out_bar, ladj_bar, params):
+        """The inverse's pullback at y: one bjx_sylvester_inv_vjp launch for ȳ (and z, when the parameters are asked for); the parameter
+        cotangents are MINUS the forward parameter pullback at z with the cotangents (ȳ, c) — the implicit-function rule of
+        `_vjp_params_inverse`; the forward rule is linear in its cotangents, so its four small results are negated, not ȳ."""
+        self._refuse_inverse()
+        yc, dim, batch, vec = _prep(y)
+        gc, gdim, gbatch, _ = _prep(out_bar)
+        if (gdim, gbatch) != (dim, batch) or gc.dtype != yc.dtype:
+            raise ValueError("DimensionMismatch: out_bar must have the shape and dtype of the output")
+        q, r, rt, b = self._tables(yc, dim)
+        lb = _ladj_bar(ladj_bar, batch, yc)
+        ctx = context(yc.device)
+        yb = _empty(dim, batch, yc, vec)
+        pre = _empty(dim, batch, yc, vec) if params else None
+        rc = L.load().bjx_sylvester_inv_vjp(ctx.h, _dt(yc), _ptr(q), _ptr(r), _ptr(rt), _ptr(b), self.n_units, _ptr(yc), _ptr(gc), _ptr(lb), _ptr(yb), _ptr(pre), dim, batch)
+        L.check(ctx.h, rc, "bjx_sylvester_inv_vjp")
+        if not params:
+            return yb, None
+        grads = self._params_at(ctx, q, r, rt, b, pre, yb, lb, None, dim, batch)
+        return yb, {k: 0 - g for k, g in grads.items()}      # 0 − g, not −g: the zeros below the diagonals of r̄ and r̃̄ stay +0
+
     def _pullback(self, x, out_bar, ladj_bar, inv, params):
         """-> (x_bar, {"q", "r", "r_tilde", "b"} summed over the batch with the constructor's shapes, or None): bjx_sylvester_vjp_params, its
-        all-NULL form (one launch) when `params` is false."""
+        all-NULL form (one launch) when `params` is false.  `inv`: the pullback of inverse(layer), `_pullback_inv`."""
         if inv:
-            self._wlj_inv(x, True)
+            return self._pullback_inv(x, out_bar, ladj_bar, params)
         xc, dim, batch, vec = _prep(x)
         gc, gdim, gbatch, _ = _prep(out_bar)
         if (gdim, gbatch) != (dim, batch) or gc.dtype != xc.dtype:
@@ -2246,17 +2294,26 @@ class SylvesterLayer(Bijector):
             rc = fn(ctx.h, _dt(xc), _ptr(q), _ptr(r), _ptr(rt), _ptr(b), M, _ptr(xc), _ptr(gc), _ptr(lb), _ptr(xb), None, None, None, None, dim, batch)
             L.check(ctx.h, rc, "bjx_sylvester_vjp_params")
             return xb, None
+        return xb, self._params_at(ctx, q, r, rt, b, xc, gc, lb, xb, dim, batch)
+
+    def _params_at(self, ctx, q, r, rt, b, xc, gc, lb, xb, dim, batch):
+        """The forward parameter pullback at xc with the cotangents (gc, lb) -> {"q", "r", "r_tilde", "b"}; the input cotangent goes to `xb`
+        (None: it is not wanted — the inverse's rule).  bjx_sylvester_vjp_params, or the chunked fallback over the LDS rule."""
+        M = self.n_units
         key = (xc.dtype, dim, M)
         if key not in _SYL_LDS_REFUSED:
             qb = torch.empty((M, dim), dtype=xc.dtype, device=xc.device).T
             rb, rtb = (torch.empty((M, M), dtype=xc.dtype, device=xc.device).T for _ in range(2))
             bb = torch.empty(M, dtype=xc.dtype, device=xc.device)
-            rc = fn(ctx.h, _dt(xc), _ptr(q), _ptr(r), _ptr(rt), _ptr(b), M, _ptr(xc), _ptr(gc), _ptr(lb), _ptr(xb), _ptr(qb), _ptr(rb), _ptr(rtb), _ptr(bb), dim, batch)
+            rc = L.load().bjx_sylvester_vjp_params(ctx.h, _dt(xc), _ptr(q), _ptr(r), _ptr(rt), _ptr(b), M, _ptr(xc), _ptr(gc), _ptr(lb), _ptr(xb), _ptr(qb), _ptr(rb),
+                                                   _ptr(rtb), _ptr(bb), dim, batch)
             if rc != L.ERR_UNSUPPORTED:
                 L.check(ctx.h, rc, "bjx_sylvester_vjp_params")
-                return xb, self._shaped(qb, rb, rtb, bb)
+                return self._shaped(qb, rb, rtb, bb)
             _SYL_LDS_REFUSED.add(key)                   # the sizes were checked above: only the LDS rule is left
-        return xb, self._shaped(*self._vjp_params_chunked(ctx, q, r, rt, b, xc, gc, lb, xb, dim, batch))
+        if xb is None:                                  # the per-column entry of the fallback always writes an input cotangent
+            xb = torch.empty_like(xc)
+        return self._shaped(*self._vjp_params_chunked(ctx, q, r, rt, b, xc, gc, lb, xb, dim, batch))
 
     def _vjp_params_chunked(self, ctx, q, r, rt, b, xc, gc, lb, xb, dim, batch):
         """The fallback of `_pullback`: chunks of columns with the parameters expanded per column through bjx_sylvester_cols_vjp, the
@@ -3610,7 +3667,7 @@ def vjp(b, x, out_bar, ladj_bar=None):
         return xb
     if isinstance(base, (AmortizedPlanarLayer, AmortizedRadialLayer, AmortizedHouseholderFlow, AmortizedSylvesterLayer)):     # per-column parameters: one bjx_planar_cols_vjp / bjx_radial_cols_vjp / bjx_householder_cols_vjp / bjx_sylvester_cols_vjp launch, either direction (Sylvester: forward only)
         return base._pullback(x, out_bar, ladj_bar, inv, False)[0]
-    if isinstance(base, SylvesterLayer):             # shared parameters: the all-NULL form of bjx_sylvester_vjp_params, one launch (forward only)
+    if isinstance(base, SylvesterLayer):             # shared parameters: the all-NULL form of bjx_sylvester_vjp_params, or bjx_sylvester_inv_vjp for the inverse of a layer built with orthonormal=True; one launch
         return base._pullback(x, out_bar, ladj_bar, inv, False)[0]
     if isinstance(base, HouseholderLayer):
         # y = U x with U orthogonal and symmetric factors: x̄ = Uᵀȳ = the other direction's map of ȳ (log-det 0: ladj_bar adds nothing)
@@ -4105,7 +4162,10 @@ def vjp_params(b, x, out_bar, ladj_bar=None):
     the key of an absent parameter is omitted.
     For an AmortizedSylvesterLayer: (x_bar, {"q", "r", "r_tilde", "b"}) PER COLUMN, not summed, one launch (its inverse is not built: NotImplementedError).
     For a HouseholderLayer or its inverse: (x_bar, {"v"}) summed over the batch, with the constructor's shape (bjx_householder_vjp_params).
-    For a SylvesterLayer: (x_bar, {"q", "r", "r_tilde", "b"}) summed over the batch, with the constructor's shapes (bjx_sylvester_vjp_params; its inverse is not built: NotImplementedError).
+    For a SylvesterLayer: (x_bar, {"q", "r", "r_tilde", "b"}) summed over the batch, with the constructor's shapes (bjx_sylvester_vjp_params).  For its inverse, served
+    where the layer was built with orthonormal=True (NotImplementedError otherwise): (y_bar, the same dictionary) by the implicit-function rule — one
+    bjx_sylvester_inv_vjp launch for ȳ and z, the forward parameter pullback at z with the cotangents (ȳ, c), four negations; q̄ is the cotangent in the
+    ambient space, q a free parameter of the forward forms.
     For a RationalQuadraticSpline or its inverse: (x_bar, {"widths", "heights", "derivatives"[, "raw_widths", ...]}) — see _vjp_params_rqs
     (a per-column spline, 3-D parameters: the per-column cotangents in its own form, see _rqs_cols_pullback).
     For a Coupling or its inverse: (x_bar, grads) with the cotangents of θ's outputs — {"scale", "shift"} per column (affine law),
@@ -4128,7 +4188,7 @@ def vjp_params(b, x, out_bar, ladj_bar=None):
         inv = isinstance(b, Inverse)                    # (x_bar, {"v"}) summed over the batch: one pass and its folds, either direction
         return (b.orig if inv else b)._vjp_params(x, out_bar, ladj_bar, inv)
     if isinstance(b, SylvesterLayer) or (isinstance(b, Inverse) and isinstance(b.orig, SylvesterLayer)):
-        inv = isinstance(b, Inverse)                    # (x_bar, {"q", "r", "r_tilde", "b"}) summed over the batch: one pass and its folds (forward only)
+        inv = isinstance(b, Inverse)                    # (x_bar, {"q", "r", "r_tilde", "b"}) summed over the batch: one pass and its folds; the inverse of an orthonormal layer through the implicit-function rule
         return (b.orig if inv else b)._pullback(x, out_bar, ladj_bar, inv, True)
     if isinstance(b, Inverse) and isinstance(b.orig, (PlanarLayer, RadialLayer, AmortizedPlanarLayer)):
         return _vjp_params_inverse(b, x, out_bar, ladj_bar)

@@ -34,7 +34,7 @@
  * and a mixture of null and non-null parameter cotangents are BJX_ERR_ARG.  Every refusal happens before anything is launched.
  * No host synchronisation and no allocation beyond the context's partials.  No atomics: the same call returns the same bits.
  *
- * Not here: the inverse map, the fused parameter pullback of shapes over the LDS rule, a fused log-density pass, the
+ * Not here: the inverse map (bjx_sylvester_inv.h, for Q'Q = I), the fused parameter pullback of shapes over the LDS rule, a fused log-density pass, the
  * orthogonalisation of Q, columns taller than a lane group holds, the Julia binding. */
 #ifndef BJX_SYLVESTER_H
 #define BJX_SYLVESTER_H
